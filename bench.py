@@ -20,6 +20,13 @@ Inputs are resident in HBM before the timed region; 12 (logits, grad) buffer pai
 are captured into one hipGraph so the measurement is not host-launch-bound; timing is HIP events
 on the launch stream, bracketed by barrier + synchronize, MAX over ranks.
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`,
+`config`, `device_status`).  `--dump-outputs DIR` then writes what the last timed step computed -- the arrays
+a caller of the step receives -- as DIR/<name>.npy (float32 / float64): `grad` (dL/dlogits of that step's
+buffer pair), `pi` (the sample weights after the E-step), `residuals`, `loss`, `train_acc`, `estep_iters`.
+The inputs are seeded, so the same arguments give the same inputs in every run.
+
+With `--full` the run goes on, after the headline and the dump, with everything below.
 Extra objects on the JSON line: `roofline` (the streaming M-step kernel in the form train_rlvi runs -- no
 caller hint --, algorithmic bytes 2*C*4+24 per sample against 8 TB/s, next to a flat nontemporal copy of the
 same bytes in the same rotation and graph: `copy_same_bytes_us`, `frac_of_copy`), `cpu_baseline` (the CPU
@@ -77,7 +84,40 @@ def parse():
     ap.add_argument("--debug-absent-peer", type=int, default=-1,
                     help="test hook: this rank never joins the start-up self-check of the sharded E-step, so "
                          "the others' waits run into their bound and every rank lands on the replicated path")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the parity gate against the CPU oracle, the per-kernel legs "
+                         "(roofline, parts, parts.configs, parts.epoch) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20      # cap on everything --dump-outputs writes
+
+
+def dump_outputs(path, grad, weights, residuals, out, iters):
+    """The last timed step's results as a caller of the step receives them.  The gradient is written whole
+    when it fits under DUMP_BYTES; otherwise a fixed seeded sample of its rows (`grad_rows` holds their
+    indices)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {"pi": weights.cpu().numpy().astype(np.float32),
+              "residuals": residuals.cpu().numpy().astype(np.float32),
+              "loss": out[0:1].cpu().numpy().astype(np.float32),
+              "train_acc": out[1:2].cpu().numpy().astype(np.float32),
+              "estep_iters": iters.cpu().numpy().astype(np.float64)}
+    room = DUMP_BYTES - sum(v.nbytes for v in arrays.values())
+    B, C = grad.shape
+    if B * C * 4 <= room:
+        arrays["grad"] = grad.cpu().numpy().astype(np.float32)
+    else:
+        keep = room // (C * 4 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrays["grad"] = grad[torch.from_numpy(rows).to(grad.device)].cpu().numpy().astype(np.float32)
+        arrays["grad_rows"] = rows.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def free_port():
@@ -620,7 +660,7 @@ def main():
         step(0, ws)
         torch.cuda.synchronize()
         it_gpu = int(iters.item())
-    if rank == 0 and world == 1 and not a.profile_only:
+    if rank == 0 and world == 1 and a.full and not a.profile_only:
         from oracle import rlvi_oracle as O        # the checker, never the thing measured
         res_o = np.zeros(N, np.float32)
         w_o = w_before.cpu().numpy()
@@ -726,6 +766,9 @@ def main():
             ms_total = timed(step, K, W, use_graph)
     ms_step = ms_total / K
     value = (B * world) / (ms_step * 1e-3)
+    if a.dump_outputs and rank == 0:
+        # the last timed step was step W + K - 1: its gradient is in that step's buffer of the rotation
+        dump_outputs(a.dump_outputs, grads[(W + K - 1) % ROTATE], weights, residuals, out, iters)
     # which physical GPUs ran: the PCI bus id of every rank's device (the same id in every process whatever the
     # visible-device masks made of the ordinals).  Ranks that share a device are a protocol check, never an
     # N-GPU measurement: n_gpus is the number of DISTINCT devices and the line says not_measured.
@@ -760,15 +803,30 @@ def main():
                    **({"same_device": True} if (a.same_device and world > 1) else {}),
                    "launch": launch_mode.get("step", "eager"), "estep_dist": estep_mode[0],
                    "mstep_logits": "default form, no caller hint (what train_rlvi runs); the hinted form is "
-                                   "parts.mstep_hinted_us",
+                                   "parts.mstep_hinted_us (--full)",
                    **({"estep_dist_note": estep_note} if estep_note else {}),
                    **({"estep_dist_setup_s": round(setup_s, 3)} if setup_s is not None else {})},
     }
     if not_measured is not None:
         result["not_measured"] = not_measured
-    if a.profile_only:
+
+    def finish():
+        st = ws.status()
+        for ev in status_log:
+            st |= int(ev["status"])
+        result["device_status"] = st      # OR over every leg of this run (0 = no device-side condition anywhere)
+        if status_log:
+            result["device_status_events"] = status_log
         if rank == 0:
             print(json.dumps(result))
+        if use_dist:
+            dist.barrier()
+            for p in peers_keep:
+                p.close()
+            dist.destroy_process_group()
+
+    if a.profile_only or not a.full:
+        finish()
         return
 
     # per-kernel legs (same buffers, same rotation): the HBM-bound M-step kernel and the
@@ -943,12 +1001,6 @@ def main():
                        "mstep_samples_per_s": B / (ms_m * 1e-3)}
     result["parts"].update(extra)
     result["parity"] = parity
-    st = ws.status()
-    for ev in status_log:
-        st |= int(ev["status"])
-    result["device_status"] = st          # OR over every leg of this run (0 = no device-side condition anywhere)
-    if status_log:
-        result["device_status_events"] = status_log
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N=1)
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
@@ -1046,13 +1098,7 @@ def main():
             "parts": {k: round(v, 1) for k, v in parts_cpu.items()},
             "leg_seconds": round(time.perf_counter() - t_leg, 1),
         }
-    if rank == 0:
-        print(json.dumps(result))
-    if use_dist:
-        dist.barrier()
-        for p in peers_keep:
-            p.close()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

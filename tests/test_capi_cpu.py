@@ -239,6 +239,35 @@ def test_bench_plans_its_ranks_and_says_what_it_could_not_measure():
         assert rec["n_gpus"] == 0 and rec["value"] is None and rec["not_measured"] == "2 requested, 0 visible"
 
 
+def test_bench_dump_outputs_stays_under_its_cap(monkeypatch, tmp_path):
+    """bench.dump_outputs writes the step's arrays as float32 / float64 .npy files; a gradient that does not fit
+    under the cap is written as a fixed seeded sample of its rows, with their indices beside it."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, C = 300, 7
+    grad = torch.arange(B * C, dtype=torch.float32).reshape(B, C)
+    w, r = torch.rand(B), torch.rand(B)
+    out, it = torch.tensor([1.5, 42.0, 0.0, 0.0]), torch.tensor([9], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "whole"), grad, w, r, out, it)
+    g = np.load(tmp_path / "whole" / "grad.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, grad.numpy())
+    assert np.load(tmp_path / "whole" / "estep_iters.npy").dtype == np.float64
+    assert float(np.load(tmp_path / "whole" / "train_acc.npy")[0]) == 42.0
+    assert not (tmp_path / "whole" / "grad_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 1024)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), grad, w, r, out, it)
+        files = list((tmp_path / run).iterdir())
+        assert sum(np.load(f).nbytes for f in files) <= 8 * 1024
+    rows = np.load(tmp_path / "a" / "grad_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < B
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "grad_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.npy"), grad.numpy()[rows.astype(np.int64)])
+
+
 def test_package_import_selects_the_dmabuf_ipc_mode(monkeypatch):
     """Multi-process GPU work (RCCL, the peers' inboxes) needs HSA_ENABLE_IPC_MODE_LEGACY=0 before the runtime
     starts: importing the package defaults it and never overrides an explicit setting."""

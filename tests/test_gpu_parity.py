@@ -1840,7 +1840,8 @@ def test_bench_two_ranks_on_one_gpu(mode, gpu):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(root, "bench.py"),
                         "--gpus", "2", "--steps", "6", "--warmup", "2", "--rows", "32768", "--backend", "gloo",
-                        "--same-device", "--no-cpu-baseline", "--no-epoch-legs", "--estep-dist", mode], capture_output=True,
+                        "--same-device", "--no-cpu-baseline", "--no-epoch-legs", "--estep-dist", mode, "--full"],
+                       capture_output=True,
                        text=True, timeout=300,
                        env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -1859,7 +1860,7 @@ def test_bench_two_ranks_on_one_gpu(mode, gpu):
     assert res["value"] > 0
 
 
-def _run_bench(args, timeout=400, env_extra=None):
+def _run_bench(args, timeout=400, env_extra=None, full=True):
     import json
     import os
     import subprocess
@@ -1867,7 +1868,8 @@ def _run_bench(args, timeout=400, env_extra=None):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(env_extra or {})
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--no-epoch-legs"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--no-epoch-legs"] +
+                       (["--full"] if full else []),
                        capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p, [json.loads(ln) for ln in lines]
@@ -1934,6 +1936,32 @@ def test_bench_absent_peer_lands_on_the_replicated_path_in_bounded_time(gpu):
     assert any(e["leg"] == "sharded self-check" and e["status"] & 2 for e in ev)
     assert all(e["leg"] == "sharded self-check" for e in ev)      # the timed legs themselves ran clean
     assert res["value"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """Without --full the bench prints the headline only (no per-kernel legs, parity gate or CPU baseline);
+    `ms_per_step` is the timed region over --steps steps.  --dump-outputs writes the last timed step's arrays:
+    float32 / float64, a gradient whose rows sum to zero (softmax minus one-hot, times pi), pi in [0, 1]."""
+    import os
+    B, C = 8192, 100
+    p, recs = _run_bench(["--steps", "5", "--warmup", "2", "--rows", str(B), "--classes", str(C),
+                          "--dump-outputs", str(tmp_path)], full=False)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(recs) == 1
+    res = recs[0]
+    assert res["steps"] == 5 and res["warmup"] == 2 and res["device_status"] == 0
+    assert res["unit"] == "samples/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert abs(res["value"] - B / (res["ms_per_step"] * 1e-3)) <= 1e-6 * res["value"]
+    assert not {"parts", "roofline", "parity", "cpu_baseline"} & set(res)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(got) == {"grad", "pi", "residuals", "loss", "train_acc", "estep_iters"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    g, pi = got["grad"], got["pi"]
+    assert g.shape == (B, C) and pi.shape == (B,) and got["residuals"].shape == (B,)
+    assert np.isfinite(g).all() and np.isfinite(pi).all() and pi.min() >= 0 and pi.max() <= 1
+    assert np.abs(g.astype(np.float64).sum(axis=1)).max() <= 1e-4 * np.abs(g).max()
+    assert got["estep_iters"][0] >= 1 and np.isfinite(got["loss"][0]) and 0 <= got["train_acc"][0] <= 100
 
 
 def oracle_pi(oracle, r):

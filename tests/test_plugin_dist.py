@@ -185,6 +185,7 @@ def _worker_peers_without_gpu(rank, world, port, q):
     try:
         from rlvi_amd import _lib
         from rlvi_amd import dist as rdist
+        assert not torch.cuda.is_available(), "the worker sees a GPU"
 
         class NoWs:
             ptr = None
@@ -203,13 +204,11 @@ def _worker_peers_without_gpu(rank, world, port, q):
 
 
 @pytest.mark.timeout(120)
-def test_peer_setup_fails_loudly_and_on_every_rank_without_a_gpu():
+def test_peer_setup_fails_loudly_and_on_every_rank_without_a_gpu(monkeypatch):
     """The sharded E-step's inboxes are device memory: on a box without a GPU the set-up must raise the
     same RlviError on every rank (the ranks agree on the failure before anyone leaves), never hang and
-    never fall back to anything."""
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("needs a box without a GPU")
+    never fall back to anything.  The ranks start with every GPU hidden, so a box with one runs this too."""
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

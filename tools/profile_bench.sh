@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box: (1) rocprofv3 --kernel-trace --stats of the bench command, (2) two separate
-# PMC passes (FETCH_SIZE, WRITE_SIZE) as MI355X_MICROARCH.md prescribes, (3) the plain bench line.
+# PMC passes (FETCH_SIZE, WRITE_SIZE) as MI355X_MICROARCH.md prescribes, (3) the full bench line.
 # Usage: tools/profile_bench.sh <tag>
 tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
@@ -14,5 +14,5 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $ARG
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 $ARGS > $out/pmc_write/bench.json 2> $out/pmc_write/err.log || exit 1
 python3 tools/prof_summary.py $out $out/summary.md
 grep -E "rlvi::" $out/summary.md | cut -c1-170
-python3 bench.py > $out/bench.json 2> $out/bench.err || exit 1
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 cat $out/bench.json
