@@ -95,7 +95,7 @@ int rlvi_workspace_clear_status(void *ws, void *stream);
  * RLVI_E_SHAPE for an unknown name. */
 int rlvi_workspace_set_option(void *ws, const char *name, int value);
 /* Which form the last M-step launch on this workspace took (tests of the dispatch): 0 none yet, 1 register rows,
- * 2 wave tiles in four-wave workgroups, 3 wave tiles in 16-wave workgroups, 4 word-wise bf16 wave tiles (odd row
+ * 2 wave tiles in four-wave workgroups, 3 wave tiles in 16-wave workgroups, 4 word-wise bf16 / fp16 wave tiles (odd row
  * lengths), 5 long rows (more than 512 vectors per row: a wave or a workgroup per row, three passes); + 16 with a timed hold. */
 int rlvi_workspace_last_mstep_form(const void *ws);
 /* Forget the guesses earlier calls left for the next one (E-step trajectory and minimum, threshold key). */
@@ -143,6 +143,21 @@ int rlvi_mstep_fwd_bwd_bf16(const uint16_t *logits, int64_t ld, const int64_t *l
                             int64_t N, int64_t B, int64_t C, float inv_scale,
                             uint16_t *grad_logits, int64_t ldg, float *out, void *ws,
                             void *stream);
+
+/* fp16 variant of the M-step (torch.autocast's default dtype): logits / grad_logits are IEEE binary16 (passed as
+ * their 16-bit patterns), arithmetic is fp32 on the exactly widened values.  The same forms as the bf16 entry --
+ * evaluation form (weights == NULL), ACCUMULATE mode (out == NULL), strided rows, RLVI_ST_RANGE -- and at every
+ * shape the same kernel form as bf16 (same bytes; rlvi_workspace_last_mstep_form shows it).
+ *   grad_scale  NULL, or a DEVICE pointer to one fp32 loss scale (torch.amp.GradScaler's scale tensor), read by the
+ *               kernel (no host sync per batch): grad_logits = inv_scale * (*grad_scale) * pi_i * (softmax - onehot),
+ *               rounded ONCE to fp16 -- nearest even, subnormals kept, +-inf on overflow (what the scaler's inf check
+ *               looks for), NaN kept.  The loss, `out`, the residuals and the accumulate-mode records never see the
+ *               scale.  4-byte aligned (RLVI_E_ALIGN otherwise).
+ */
+int rlvi_mstep_fwd_bwd_f16(const uint16_t *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
+                           const float *weights, float *residuals, int64_t N, int64_t B, int64_t C,
+                           float inv_scale, const float *grad_scale, uint16_t *grad_logits, int64_t ldg,
+                           float *out, void *ws, void *stream);
 
 /* out[4] = scale * {sum loss_b, sum top-1 %_b}, sum pi*l, hits over the accumulated batches;
  * clears the records (scale = 1/batches gives the reference's train_acc, train_rlvi.py:105). */
@@ -267,6 +282,10 @@ int rlvi_topk_hits_f32(const float *logits, int64_t ld, const int64_t *labels, i
                        const int32_t *ks, int nk, int32_t *hits, void *stream);
 int rlvi_topk_hits_bf16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C,
                         const int32_t *ks, int nk, int32_t *hits, void *stream);
+/* fp16 logits (16-bit patterns of IEEE binary16): the rank count on the exactly widened values, so the hits equal
+ * rlvi_topk_hits_f32 on the same logits converted to fp32. */
+int rlvi_topk_hits_f16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C,
+                       const int32_t *ks, int nk, int32_t *hits, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * In-batch fused E+M (online order, online-learning/main.py:296-299 applied to a logit block):

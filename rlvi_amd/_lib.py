@@ -50,6 +50,8 @@ SIGNATURES = {
                                       _vp, _i64, _vp, _vp, _vp]),
     "rlvi_mstep_fwd_bwd_bf16": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32,
                                        _vp, _i64, _vp, _vp, _vp]),
+    "rlvi_mstep_fwd_bwd_f16": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32,
+                                      _vp, _vp, _i64, _vp, _vp, _vp]),
     "rlvi_mstep_reduce_f32": (_int, [_vp, _f64, _vp, _vp]),
     "rlvi_estep_deep_f32": (_int, [_vp, _vp, _i64, _f32, _int, _vp, _vp, _vp, _vp]),
     "rlvi_epoch_end_f32": (_int, [_vp, _vp, _i64, _f32, _int, _int, _f32, _vp, _i64, _vp, _vp,
@@ -60,6 +62,7 @@ SIGNATURES = {
     "rlvi_select_smallest_f32": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "rlvi_topk_hits_f32": (_int, [_vp, _i64, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp]),
     "rlvi_topk_hits_bf16": (_int, [_vp, _i64, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp]),
+    "rlvi_topk_hits_f16": (_int, [_vp, _i64, _vp, _i64, _i64, ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp]),
     "rlvi_fused_em_f32": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _int,
                                  _vp, _i64, _vp, _vp, _vp, _vp]),
     "rlvi_update_weights_f64": (_int, [_vp, _i64, _f64, _int, _vp, _vp, _vp, _vp]),

@@ -5,7 +5,7 @@
 // reached from :96.
 //
 // Bound: HBM.  Algorithmic bytes per sample = 2*C*s + 24 (logits read + grad write + label 8 +
-// index 8 + pi gather 4 + residual scatter 4), s = 4 (fp32) or 2 (bf16).
+// index 8 + pi gather 4 + residual scatter 4), s = 4 (fp32) or 2 (bf16, fp16).
 //
 // Mapping (gfx950, 64-lane waves): a row is owned by a group of G consecutive lanes, every lane
 // holding K vectors of V elements (16 B per lane per load when the row pitch allows), so a wave
@@ -79,61 +79,70 @@ struct VecIO<float, 1> : VecIOBase<float, 1, VecIO<float, 1>> {
     static __device__ __forceinline__ void load(const float *p, float (&v)[1]) { v[0] = *p; }
     static __device__ __forceinline__ void store(float *p, const float (&v)[1]) { *p = v[0]; }
 };
-template <>
-struct VecIO<uint16_t, 8> : VecIOBase<uint16_t, 8, VecIO<uint16_t, 8>> {
-    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[8]) {
+// 2-byte elements (T = uint16_t: bf16, T = f16_t: fp16): widened to fp32 and narrowed back through Half<T>
+template <typename T>
+struct VecIO<T, 8> : VecIOBase<T, 8, VecIO<T, 8>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
         const uint4 t = *reinterpret_cast<const uint4 *>(p);
         const uint32_t w[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+            v[2 * i] = Half<T>::lo(w[i]);
+            v[2 * i + 1] = Half<T>::hi(w[i]);
         }
     }
-    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[8]) {
+    static __device__ __forceinline__ void store(T *p, const float (&v)[8]) {
         uint32_t w[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            w[i] = f32x2_to_bf16x2(v[2 * i], v[2 * i + 1]);
+            w[i] = Half<T>::narrow2(v[2 * i], v[2 * i + 1]);
         *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
     }
 };
-template <>
-struct VecIO<uint16_t, 4> : VecIOBase<uint16_t, 4, VecIO<uint16_t, 4>> {
-    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[4]) {
+template <typename T>
+struct VecIO<T, 4> : VecIOBase<T, 4, VecIO<T, 4>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
         const uint2 t = *reinterpret_cast<const uint2 *>(p);
-        v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xFFFF0000u);
-        v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xFFFF0000u);
+        v[0] = Half<T>::lo(t.x); v[1] = Half<T>::hi(t.x);
+        v[2] = Half<T>::lo(t.y); v[3] = Half<T>::hi(t.y);
     }
-    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[4]) {
+    static __device__ __forceinline__ void store(T *p, const float (&v)[4]) {
         uint2 t;
-        t.x = f32x2_to_bf16x2(v[0], v[1]);
-        t.y = f32x2_to_bf16x2(v[2], v[3]);
+        t.x = Half<T>::narrow2(v[0], v[1]);
+        t.y = Half<T>::narrow2(v[2], v[3]);
         *reinterpret_cast<uint2 *>(p) = t;
     }
 };
-template <>
-struct VecIO<uint16_t, 2> : VecIOBase<uint16_t, 2, VecIO<uint16_t, 2>> {
-    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[2]) {
+template <typename T>
+struct VecIO<T, 2> : VecIOBase<T, 2, VecIO<T, 2>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[2]) {
         const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
-        v[0] = __uint_as_float(t << 16); v[1] = __uint_as_float(t & 0xFFFF0000u);
+        v[0] = Half<T>::lo(t); v[1] = Half<T>::hi(t);
     }
-    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[2]) {
-        *reinterpret_cast<uint32_t *>(p) = f32x2_to_bf16x2(v[0], v[1]);
+    static __device__ __forceinline__ void store(T *p, const float (&v)[2]) {
+        *reinterpret_cast<uint32_t *>(p) = Half<T>::narrow2(v[0], v[1]);
     }
 };
-template <>
-struct VecIO<uint16_t, 1> : VecIOBase<uint16_t, 1, VecIO<uint16_t, 1>> {
-    static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[1]) {
-        v[0] = bf16_to_f32(*p);
+template <typename T>
+struct VecIO<T, 1> : VecIOBase<T, 1, VecIO<T, 1>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[1]) {
+        v[0] = Half<T>::widen(*reinterpret_cast<const uint16_t *>(p));
     }
-    static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[1]) {
-        *p = f32_to_bf16(v[0]);
+    static __device__ __forceinline__ void store(T *p, const float (&v)[1]) {
+        *reinterpret_cast<uint16_t *>(p) = Half<T>::narrow(v[0]);
     }
 };
 
 constexpr int MSTEP_THREADS = 256;
 constexpr int MSTEP_WAVES = MSTEP_THREADS / WAVE;
+
+// The gradient's factor: inv_scale times the loss scale that a GradScaler keeps on the device (grad_scale, fp16
+// entries; NULL: none).  Read by the kernel, so a training loop needs no host sync per batch.  The loss, the records
+// and the residuals never see the scale.  (Wave-uniform: readfirstlane keeps it in an SGPR, as inv_scale is.)
+__device__ __forceinline__ float grad_gain(float inv_scale, const float *grad_scale) {
+    const float g = grad_scale != nullptr ? inv_scale * *grad_scale : inv_scale;
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g)));
+}
 
 // Per-block partial record.  accum == 0: overwrite (a finalize launch follows); accum == 1: add
 // to what earlier mini-batches of this epoch left there (rlvi_epoch_end_f32 reduces and clears).
@@ -168,14 +177,15 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
     const T *__restrict__ logits, int64_t ld, const int64_t *__restrict__ labels,
     const int64_t *__restrict__ idx, const float *__restrict__ weights,
     float *__restrict__ residuals, int64_t N, int64_t B, int C, int kact, float inv_scale,
-    T *__restrict__ grad, int64_t ldg, double *__restrict__ part, int32_t *__restrict__ status,
-    int accum, double inv_rows100, int64_t first_row) {
+    const float *__restrict__ grad_scale, T *__restrict__ grad, int64_t ldg, double *__restrict__ part,
+    int32_t *__restrict__ status, int accum, double inv_rows100, int64_t first_row) {
     constexpr int R = WAVE / G;  // rows per wave
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
     const int g = lane & (G - 1);
     const int sub = lane / G;
     const float NEG_INF = -__builtin_inff();
+    const float gscale = grad_gain(inv_scale, grad_scale);
 
     float acc = 0.0f;   // sum of pi*l over the rows whose lane-group leader this lane is
     float hits = 0.0f;
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
         const float li = logs - (zy - m);   // == -((z_y - max) - log(sum exp)), as torch evaluates it
 
         if (grad != nullptr && valid) {
-            const float gs = row_ok ? pi * inv_scale : 0.0f;   // a rejected row gets a zero gradient row
+            const float gs = row_ok ? pi * gscale : 0.0f;   // a rejected row gets a zero gradient row
             const float inv_s = gs / s;
             T *grow = grad + rr * ldg;
 #pragma unroll
@@ -316,8 +326,8 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
     const T *__restrict__ logits, int64_t ld, const int64_t *__restrict__ labels,
     const int64_t *__restrict__ idx, const float *__restrict__ weights,
     float *__restrict__ residuals, int64_t N, int64_t B, int C, float inv_scale,
-    T *__restrict__ grad, int64_t ldg, double *__restrict__ part, int32_t *__restrict__ status,
-    int accum, double inv_rows100) {
+    const float *__restrict__ grad_scale, T *__restrict__ grad, int64_t ldg, double *__restrict__ part,
+    int32_t *__restrict__ status, int accum, double inv_rows100) {
     constexpr int U = 4;                                          // vectors per lane and trip
     constexpr int RPB = MSTEP_WAVES / WPR;                        // rows per workgroup at a time
     constexpr int STEP = WPR * WAVE;                              // lanes on one row
@@ -328,6 +338,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
     __shared__ int shi[MSTEP_WAVES];
     float acc = 0.0f, hits = 0.0f;
     bool bad = false;
+    const float gscale = grad_gain(inv_scale, grad_scale);
     const int nv = C / V;                                         // (V divides C)
     const int64_t stride = (int64_t)gridDim.x * RPB;
     // (every thread of a workgroup runs the same number of trips: the barriers below are uniform)
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
         const float li = logf(s) - (zy - m);
         // ---- pass 3: the gradient
         if (grad != nullptr && valid) {
-            const float gs = row_ok ? pi * inv_scale : 0.0f;
+            const float gs = row_ok ? pi * gscale : 0.0f;
             const float inv_s = gs / s;
             T *grow = grad + rr * ldg;
             for (int k0 = t; k0 < nv; k0 += STEP * U) {
@@ -502,8 +513,8 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     const T *__restrict__ logits, const int64_t *__restrict__ labels,
     const int64_t *__restrict__ idx, const float *__restrict__ weights,
     float *__restrict__ residuals, int64_t N, int64_t nfull, int C, float inv_scale,
-    T *__restrict__ grad, double *__restrict__ part, int32_t *__restrict__ status, int accum,
-    double inv_rows100, int hold_ticks, int gen_ticks, unsigned long long *__restrict__ hold_slot,
+    const float *__restrict__ grad_scale, T *__restrict__ grad, double *__restrict__ part,
+    int32_t *__restrict__ status, int accum, double inv_rows100, int hold_ticks, int gen_ticks, unsigned long long *__restrict__ hold_slot,
     unsigned long long hold_key, int hold_cap, int hold_pct) {
     constexpr int R = WAVE / G;                                   // rows per wave tile
     constexpr int VB = V * (int)sizeof(T);                        // bytes of a lane vector
@@ -550,6 +561,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     const int row_off = sub * C * (int)sizeof(T);
     const int64_t *idxp = idx != nullptr ? idx : labels;
     const unsigned sub8 = (unsigned)sub * 8u;
+    const float gscale = grad_gain(inv_scale, grad_scale);
 
     float acc = 0.0f, hits = 0.0f;
     bool bad = false;
@@ -708,7 +720,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
             hit = hit && earlier == 0;
         }
         if (grad != nullptr) {
-            const float gs = pi * inv_scale;
+            const float gs = pi * gscale;
             const float inv_s = gs * __builtin_amdgcn_rcpf(s);
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
@@ -727,10 +739,10 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
                 // -onehot term: one read-modify-write of the label entry, ordered behind this wave's
                 // vector stores (LDS operations of a wave complete in order); the lanes of a group
                 // all write the same value
-                // (gs = pi * inv_scale unrounded inside the fma: spelled out so that fused_em.hip,
+                // (gs = pi * gscale unrounded inside the fma: spelled out so that fused_em.hip,
                 //  which promises the same bits, does not depend on what the compiler contracts)
                 float *zf = reinterpret_cast<float *>(zrow);
-                zf[y] = fmaf(-inv_scale, pi, zf[y]);
+                zf[y] = fmaf(-gscale, pi, zf[y]);
             }
         }
         if (g == 0 && okrow && residuals != nullptr) residuals[ix] = li;
@@ -809,21 +821,23 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
 }
 
 // ---------------------------------------------------------------------------------------
-// bf16 rows of an ODD number of elements (C = 101: 202-byte rows, every other row starts in the
+// bf16 / fp16 rows of an ODD number of elements (C = 101: 202-byte rows, every other row starts in the
 // middle of a 32-bit word), at least 32 768 of them (round 4; the round-3 verdict's item 4b).  The general wave tile
 // reads such a row one 2-byte element per LDS instruction (27.5 us at 65 536 x 101, so the launcher sent the shape
 // to the register-row kernel: 14.3 us).  Here the tile is the same flat 16-B/lane stream into LDS, but a lane owns a
 // CONTIGUOUS segment of its row -- four lanes per row, L = ceil(C / 4) elements each -- and reads it as 32-bit words
 // from the word its first element lies in; v_alignbit re-aligns the words of an odd start, a shift and a mask widen the
-// two halves.  The gradient goes back in place as bf16 halves (v_cvt_pk_bf16_f32 per pair, one 16-bit LDS store per
-// element: a word of the tile may belong to two lanes, or two rows) and leaves as flat 16-B stores.
+// two halves (Half<T>: bf16 or fp16).  The gradient goes back in place as 2-byte halves (v_cvt_pk_bf16_f32 or
+// v_cvt_pk_f16_f32 per pair, one 16-bit LDS store per element: a word of the tile may belong to two lanes, or two
+// rows) and leaves as flat 16-B stores.
 // ---------------------------------------------------------------------------------------
-template <int KW, int WPB>
+template <typename T, int KW, int WPB>
 __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
-    const uint16_t *__restrict__ logits, const int64_t *__restrict__ labels, const int64_t *__restrict__ idx,
+    const T *__restrict__ logits, const int64_t *__restrict__ labels, const int64_t *__restrict__ idx,
     const float *__restrict__ weights, float *__restrict__ residuals, int64_t N, int64_t nfull, int C,
-    float inv_scale, uint16_t *__restrict__ grad, double *__restrict__ part, int32_t *__restrict__ status,
-    int accum, double inv_rows100) {
+    float inv_scale, const float *__restrict__ grad_scale, T *__restrict__ grad, double *__restrict__ part,
+    int32_t *__restrict__ status, int accum, double inv_rows100) {
+    static_assert(sizeof(T) == 2, "word-wise tile of 2-byte elements");
     constexpr int R = 16, G = 4, NI = 4;                          // 16 rows x <= 128 elements x 2 B <= 4 KiB
     constexpr int WTILE = NI * 1024 + 64;                         // (+ a pad: the word past a segment's end, dummy stores)
     constexpr int NE = 2 * KW;                                    // element slots of a lane
@@ -843,6 +857,7 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
     const int64_t *idxp = idx != nullptr ? idx : labels;
     const unsigned sub8 = (unsigned)sub * 8u;
     const int64_t tstride = (int64_t)gridDim.x * WPB;
+    const float gscale = grad_gain(inv_scale, grad_scale);
     float acc = 0.0f, hits = 0.0f;
     bool bad = false;
     for (int64_t t = (int64_t)blockIdx.x * WPB + wave; t < nfull; t += tstride) {
@@ -873,7 +888,7 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
         const int y = (int)y64;
         const uint32_t *w32 = reinterpret_cast<const uint32_t *>(wtile);
         const uint16_t *h16 = reinterpret_cast<const uint16_t *>(wtile);
-        const float zy = bf16_to_f32(h16[sub * C + y]);
+        const float zy = Half<T>::widen(h16[sub * C + y]);
         uint32_t w[KW + 1];
 #pragma unroll
         for (int k = 0; k <= KW; ++k) w[k] = w32[W0 + k];
@@ -881,8 +896,8 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
 #pragma unroll
         for (int k = 0; k < KW; ++k) {
             const uint32_t x = __builtin_amdgcn_alignbit(w[k + 1], w[k], shift);      // elements 2k, 2k + 1
-            v[2 * k] = __uint_as_float(x << 16);
-            v[2 * k + 1] = __uint_as_float(x & 0xFFFF0000u);
+            v[2 * k] = Half<T>::lo(x);
+            v[2 * k + 1] = Half<T>::hi(x);
         }
         const float NEG_INF = -__builtin_inff();
         float m = NEG_INF;
@@ -911,14 +926,14 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
                 const uint32_t x = __builtin_amdgcn_alignbit(w[k + 1], w[k], shift);
-                const float z0 = __uint_as_float(x << 16), z1 = __uint_as_float(x & 0xFFFF0000u);
+                const float z0 = Half<T>::lo(x), z1 = Half<T>::hi(x);
                 earlier += (2 * k < cnt && z0 == m && e0 + 2 * k < y) ? 1 : 0;
                 earlier += (2 * k + 1 < cnt && z1 == m && e0 + 2 * k + 1 < y) ? 1 : 0;
             }
             hit = hit0 && group_allreduce<G>(earlier, FAdd()) == 0;
         }
         if (grad != nullptr) {
-            const float gs = pi * inv_scale;
+            const float gs = pi * gscale;
             const float inv_s = gs * __builtin_amdgcn_rcpf(s);
             const int jy = y - e0;                                // the label's slot, if it lies in this segment
             uint16_t *o16 = reinterpret_cast<uint16_t *>(wtile);
@@ -928,7 +943,7 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
                 float o0 = v[2 * k] * inv_s, o1 = v[2 * k + 1] * inv_s;
                 o0 = 2 * k == jy ? o0 - gs : o0;
                 o1 = 2 * k + 1 == jy ? o1 - gs : o1;
-                const uint32_t pk = f32x2_to_bf16x2(o0, o1);
+                const uint32_t pk = Half<T>::narrow2(o0, o1);
                 o16[2 * k < cnt ? E0 + 2 * k : dummy] = (uint16_t)(pk & 0xFFFFu);
                 o16[2 * k + 1 < cnt ? E0 + 2 * k + 1 : dummy] = (uint16_t)(pk >> 16);
             }
@@ -987,8 +1002,8 @@ __global__ __launch_bounds__(256) void mstep_finalize_kernel(double *__restrict_
 template <typename T, int V, int G, int KMAX>
 static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
                         const float *weights, float *residuals, int64_t N, int64_t B, int C,
-                        int kact, float inv_scale, T *grad, int64_t ldg, float *out, void *ws,
-                        hipStream_t st) {
+                        int kact, float inv_scale, const float *grad_scale, T *grad, int64_t ldg, float *out,
+                        void *ws, hipStream_t st) {
     constexpr int R = WAVE / G;
     constexpr int WPB = 4;                          // waves per workgroup of the wave-tile form
     const int cus = device_info().cus;
@@ -1086,8 +1101,8 @@ static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, cons
                         attr_dev = cur_dev;
                     }
                     return launch(kern, dim3((unsigned)nb16), dim3(WPB16 * WAVE), lds16, st, logits, labels, idx,
-                                  weights, residuals, N, nfull, C, inv_scale, grad, part, status, accum, inv_rows100,
-                                  hold_ticks, 0, (unsigned long long *)nullptr, 0ull, 0, 100);
+                                  weights, residuals, N, nfull, C, inv_scale, grad_scale, grad, part, status, accum,
+                                  inv_rows100, hold_ticks, 0, (unsigned long long *)nullptr, 0ull, 0, 100);
                 };
                 rc = kact == KMAX ? go(mstep_wave_kernel<T, V, G, KMAX, WPB16, true>)
                                   : go(mstep_wave_kernel<T, V, G, KMAX, WPB16, false>);
@@ -1100,19 +1115,21 @@ static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, cons
         if (cuwide_done) {
         } else if (kact == KMAX)
             rc = launch(mstep_wave_kernel<T, V, G, KMAX, WPB, true>, dim3((unsigned)nb), dim3(WPB * WAVE),
-                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad,
-                        part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap, hold_pct);
+                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad_scale,
+                        grad, part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap,
+                        hold_pct);
         else
             rc = launch(mstep_wave_kernel<T, V, G, KMAX, WPB, false>, dim3((unsigned)nb), dim3(WPB * WAVE),
-                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad,
-                        part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap, hold_pct);
+                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad_scale,
+                        grad, part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap,
+                        hold_pct);
         const int64_t done = nfull * R;
         if (rc == 0 && done < B) {
             // the B mod R trailing rows: one workgroup of the register-row kernel, adding to record 0
             rc = launch(mstep_kernel<T, V, G, KMAX>, dim3(1), dim3(MSTEP_THREADS), 0, st,
                         logits + done * ld, ld, labels + done, idx != nullptr ? idx + done : idx, weights,
-                        residuals, N, B - done, C, kact, inv_scale, grad != nullptr ? grad + done * ldg : grad,
-                        ldg, part, status, 1, inv_rows100, done);
+                        residuals, N, B - done, C, kact, inv_scale, grad_scale,
+                        grad != nullptr ? grad + done * ldg : grad, ldg, part, status, 1, inv_rows100, done);
         }
     } else {
         const int max_blocks = tune_get("RLVI_MSTEP_BLOCKS", MSTEP_MAX_BLOCKS);
@@ -1123,8 +1140,8 @@ static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, cons
         if (nb < 1) nb = 1;
         ws_note_mstep(ws, 1);
         rc = launch(mstep_kernel<T, V, G, KMAX>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                    logits, ld, labels, idx, weights, residuals, N, B, C, kact, inv_scale, grad, ldg,
-                    part, status, accum, inv_rows100, (int64_t)0);
+                    logits, ld, labels, idx, weights, residuals, N, B, C, kact, inv_scale, grad_scale, grad,
+                    ldg, part, status, accum, inv_rows100, (int64_t)0);
     }
     if (rc != 0 || out == nullptr) return rc;
     // the finalize pass clears what it read: records are all-zero outside an accumulate sequence
@@ -1137,13 +1154,13 @@ static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, cons
 template <typename T, int V>
 static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
                        const float *weights, float *residuals, int64_t N, int64_t B, int C,
-                       float inv_scale, T *grad, int64_t ldg, float *out, void *ws,
+                       float inv_scale, const float *grad_scale, T *grad, int64_t ldg, float *out, void *ws,
                        hipStream_t st) {
     const int nv = (C + V - 1) / V;
     const int force_g = tune_get("RLVI_MSTEP_G", 0);
 #define RLVI_CASE(G_, K_)                                                                        \
     return launch_mstep<T, V, G_, K_>(logits, ld, labels, idx, weights, residuals, N, B, C,      \
-                                      (nv + G_ - 1) / G_, inv_scale, grad, ldg, out, ws, st)
+                                      (nv + G_ - 1) / G_, inv_scale, grad_scale, grad, ldg, out, ws, st)
     // (bf16 in 16-byte vectors: at most FOUR vectors = 32 elements per lane, as fp32's eight -- with 64 elements a lane's
     //  serial work and its registers cost more than the shorter reductions save: tools/lab/sweep_g_bf16.sh, 16 384 x 256
     //  11.2 -> 6.5 us, x 512 15.8 -> 8.6, x 1000 24.3 -> 15.8, x 2000 39.5 -> 26.7, 4096 x 1000 10.8 -> 6.6)
@@ -1207,10 +1224,12 @@ static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const
         if (nb > MSTEP_MAX_BLOCKS) nb = MSTEP_MAX_BLOCKS;
         ws_note_mstep(ws, 5);
         const int rc = wide ? launch(mstep_longrow_kernel<T, V, MSTEP_WAVES>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad, ldg, part,
+                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad,
+                                     ldg, part,
                                      reinterpret_cast<int32_t *>(base), out == nullptr ? 1 : 0, 100.0 / (double)B)
                             : launch(mstep_longrow_kernel<T, V, 1>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad, ldg, part,
+                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad,
+                                     ldg, part,
                                      reinterpret_cast<int32_t *>(base), out == nullptr ? 1 : 0, 100.0 / (double)B);
         if (rc != 0 || out == nullptr) return rc;
         return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
@@ -1239,14 +1258,15 @@ static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const
 template <typename T>
 static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
                        const float *weights, float *residuals, int64_t N, int64_t B, int64_t C,
-                       float inv_scale, T *grad, int64_t ldg, float *out, void *ws, void *stream) {
+                       float inv_scale, const float *grad_scale, T *grad, int64_t ldg, float *out, void *ws,
+                       void *stream) {
     if (!logits || !labels || !ws) return RLVI_E_NULL;
     if (!weights && idx) return RLVI_E_NULL;       // an index without the vector it indexes
     if (!weights) N = B;                            // evaluation form: identity rows, pi = 1
     if (B <= 0 || C <= 0 || N <= 0 || ld < C || (grad && ldg < C)) return RLVI_E_SHAPE;
     if (C > (1 << 20)) return RLVI_E_LIMIT;
     if (((uintptr_t)labels & 7) || ((uintptr_t)idx & 7) || ((uintptr_t)weights & 3) ||
-        ((uintptr_t)residuals & 3) || ((uintptr_t)out & 3) || ((uintptr_t)ws & 255) ||
+        ((uintptr_t)residuals & 3) || ((uintptr_t)out & 3) || ((uintptr_t)ws & 255) || ((uintptr_t)grad_scale & 3) ||
         ((uintptr_t)logits % sizeof(T)) || (grad && ((uintptr_t)grad % sizeof(T))))
         return RLVI_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1260,9 +1280,10 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
     constexpr int VMAX = 16 / (int)sizeof(T);
     const int Ci = (int)C;
     if constexpr (sizeof(T) == 2) {
-        // bf16 rows of an odd number of elements (single 2-byte elements in the general forms), at least 32 768 of
-        // them, dense, 16-byte aligned: the
-        // word-wise wave tile (mstep_bf16w_kernel); the B mod 16 trailing rows go to the register-row kernel
+        // bf16 / fp16 rows of an odd number of elements (single 2-byte elements in the general forms), at least
+        // 32 768 of them, dense, 16-byte aligned: the word-wise wave tile (mstep_bf16w_kernel); the B mod 16
+        // trailing rows go to the register-row kernel.  (Every 2-byte decision here and in dispatch_gk was tuned on
+        // bytes, not on the format: fp16 takes the form bf16 takes at every shape.)
         if (((C & 1) != 0 || tune_get("RLVI_MSTEP_BF16W", 1) == 2) && C >= 9 && C <= 127 && B >= 16 * 2048 && ld == C && (grad == nullptr || ldg == C) &&
             ((uintptr_t)logits % 16) == 0 && ((uintptr_t)grad % 16) == 0 && tune_get("RLVI_MSTEP_BF16W", 1) &&
             tune_get("RLVI_MSTEP_FORM", -1) != 0 && tune_get("RLVI_MSTEP_G", 0) == 0) {
@@ -1283,8 +1304,8 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
             int rc;
             ws_note_mstep(ws, 4);
 #define RLVI_BW(KW_)                                                                                       \
-    rc = launch(mstep_bf16w_kernel<KW_, WPB>, dim3((unsigned)nb), dim3(WPB * WAVE), lds, st, logits, labels, idx, \
-                weights, residuals, N, nfull, Ci, inv_scale, grad, part, status, accum, inv_rows100)
+    rc = launch(mstep_bf16w_kernel<T, KW_, WPB>, dim3((unsigned)nb), dim3(WPB * WAVE), lds, st, logits, labels,    \
+                idx, weights, residuals, N, nfull, Ci, inv_scale, grad_scale, grad, part, status, accum, inv_rows100)
             if (kw <= 8) RLVI_BW(8);
             else if (kw <= 13) RLVI_BW(13);
             else RLVI_BW(16);
@@ -1293,8 +1314,8 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
             if (rc == 0 && done < B)
                 rc = launch(mstep_kernel<T, 1, 16, 8>, dim3(1), dim3(MSTEP_THREADS), 0, st, logits + done * ld, ld,
                             labels + done, idx != nullptr ? idx + done : idx, weights, residuals, N, B - done, Ci,
-                            (Ci + 15) / 16, inv_scale, grad != nullptr ? grad + done * ldg : grad, ldg, part, status, 1,
-                            inv_rows100, done);
+                            (Ci + 15) / 16, inv_scale, grad_scale, grad != nullptr ? grad + done * ldg : grad, ldg,
+                            part, status, 1, inv_rows100, done);
             if (rc != 0 || out == nullptr) return rc;
             return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
         }
@@ -1302,16 +1323,16 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
     if constexpr (VMAX == 8) {
         if (ok(8))
             return dispatch_gk<T, 8>(logits, ld, labels, idx, weights, residuals, N, B, Ci,
-                                     inv_scale, grad, ldg, out, ws, st);
+                                     inv_scale, grad_scale, grad, ldg, out, ws, st);
     }
     if (ok(4))
         return dispatch_gk<T, 4>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                                 grad, ldg, out, ws, st);
+                                 grad_scale, grad, ldg, out, ws, st);
     if (ok(2))
         return dispatch_gk<T, 2>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                                 grad, ldg, out, ws, st);
+                                 grad_scale, grad, ldg, out, ws, st);
     return dispatch_gk<T, 1>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                             grad, ldg, out, ws, st);
+                             grad_scale, grad, ldg, out, ws, st);
 }
 
 }  // namespace rlvi
@@ -1322,7 +1343,7 @@ extern "C" int rlvi_mstep_fwd_bwd_f32(const float *logits, int64_t ld, const int
                                       float *grad_logits, int64_t ldg, float *out, void *ws,
                                       void *stream) {
     return rlvi::mstep_entry<float>(logits, ld, labels, idx, weights, residuals, N, B, C,
-                                    inv_scale, grad_logits, ldg, out, ws, stream);
+                                    inv_scale, nullptr, grad_logits, ldg, out, ws, stream);
 }
 
 extern "C" int rlvi_mstep_fwd_bwd_bf16(const uint16_t *logits, int64_t ld, const int64_t *labels,
@@ -1331,7 +1352,17 @@ extern "C" int rlvi_mstep_fwd_bwd_bf16(const uint16_t *logits, int64_t ld, const
                                        uint16_t *grad_logits, int64_t ldg, float *out, void *ws,
                                        void *stream) {
     return rlvi::mstep_entry<uint16_t>(logits, ld, labels, idx, weights, residuals, N, B, C,
-                                       inv_scale, grad_logits, ldg, out, ws, stream);
+                                       inv_scale, nullptr, grad_logits, ldg, out, ws, stream);
+}
+
+extern "C" int rlvi_mstep_fwd_bwd_f16(const uint16_t *logits, int64_t ld, const int64_t *labels,
+                                      const int64_t *idx, const float *weights, float *residuals,
+                                      int64_t N, int64_t B, int64_t C, float inv_scale,
+                                      const float *grad_scale, uint16_t *grad_logits, int64_t ldg,
+                                      float *out, void *ws, void *stream) {
+    return rlvi::mstep_entry<rlvi::f16_t>(reinterpret_cast<const rlvi::f16_t *>(logits), ld, labels, idx, weights,
+                                          residuals, N, B, C, inv_scale, grad_scale,
+                                          reinterpret_cast<rlvi::f16_t *>(grad_logits), ldg, out, ws, stream);
 }
 
 // Reduce (and clear) the partial records that accumulate-mode M-step calls left in the workspace.

@@ -342,4 +342,34 @@ __device__ __forceinline__ uint32_t f32x2_to_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_t));
 }
 
+// fp16 (IEEE binary16) elements are stored as _Float16; uint16_t storage always means bf16.
+typedef _Float16 f16_t;
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+
+// Widen / narrow of the two 2-byte element formats.  A 32-bit word holds element 2k in bits 15:0 and element
+// 2k + 1 in bits 31:16.  Widening is exact; narrowing rounds to nearest even, keeps subnormals (fp16), turns an
+// overflow into +-inf and keeps NaN NaN: the bits of torch's .to(dtype) of the fp32 value.
+template <typename T>
+struct Half;
+template <>
+struct Half<uint16_t> {                                           // bf16
+    static __device__ __forceinline__ float widen(uint16_t h) { return bf16_to_f32(h); }
+    static __device__ __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+    static __device__ __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+    static __device__ __forceinline__ uint16_t narrow(float f) { return f32_to_bf16(f); }
+    static __device__ __forceinline__ uint32_t narrow2(float lo, float hi) { return f32x2_to_bf16x2(lo, hi); }
+};
+template <>
+struct Half<f16_t> {                                              // fp16
+    static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(f16_t, h); }
+    static __device__ __forceinline__ float lo(uint32_t w) { return widen((uint16_t)(w & 0xFFFFu)); }
+    static __device__ __forceinline__ float hi(uint32_t w) { return widen((uint16_t)(w >> 16)); }
+    static __device__ __forceinline__ uint16_t narrow(float f) { return __builtin_bit_cast(uint16_t, (f16_t)f); }
+    // two values in one v_cvt_pk_f16_f32 (round to nearest even; not cvt_pkrtz, which truncates and saturates)
+    static __device__ __forceinline__ uint32_t narrow2(float lo, float hi) {
+        const f32x2_t v = {lo, hi};
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
+    }
+};
+
 }  // namespace rlvi

@@ -20,7 +20,8 @@ constexpr int TOPK_MAXK = 8;              // k values per call
 struct TopkList { int k[TOPK_MAXK]; };
 
 __device__ __forceinline__ float topk_widen(float v) { return v; }
-__device__ __forceinline__ float topk_widen(uint16_t v) { return bf16_to_f32(v); }
+__device__ __forceinline__ float topk_widen(uint16_t v) { return Half<uint16_t>::widen(v); }      // bf16
+__device__ __forceinline__ float topk_widen(f16_t v) { return (float)v; }                             // fp16 (exact)
 
 // G = lanes per row (a power of two, chosen by the launcher so that a lane holds at most eight elements of rows up
 // to 512 columns): 64 / G rows per wave at once, their elements asked for BEFORE the label's logit is known (the
@@ -137,4 +138,10 @@ extern "C" int rlvi_topk_hits_f32(const float *logits, int64_t ld, const int64_t
 extern "C" int rlvi_topk_hits_bf16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C,
                                    const int32_t *ks, int nk, int32_t *hits, void *stream) {
     return rlvi::topk_entry<uint16_t>(logits, ld, labels, B, C, ks, nk, hits, stream);
+}
+
+extern "C" int rlvi_topk_hits_f16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C,
+                                  const int32_t *ks, int nk, int32_t *hits, void *stream) {
+    return rlvi::topk_entry<rlvi::f16_t>(reinterpret_cast<const rlvi::f16_t *>(logits), ld, labels, B, C, ks, nk, hits,
+                                         stream);
 }

@@ -14,6 +14,7 @@ pairflip 0.45, batch sharded over the ranks) run end to end:
 
     python -m rlvi_amd.driver --dataset mnist --batch_size 4096 --n_train 54000 --n_epoch 4
     python -m torch.distributed.run --nproc-per-node 8 -m rlvi_amd.driver --dataset cifar10 --batch_size 32768
+    python -m rlvi_amd.driver --dataset cifar10 --amp fp16      # autocast + GradScaler (train_rlvi_amp)
 
 The models only produce logits and are stock torch.nn: a LeNet-shaped CNN (two 5x5 convs with 2x2
 max-pools, 120-84-C head, as models/lenet.py:17-35) and a CIFAR-style ResNet18 (3x3 stem without
@@ -31,7 +32,7 @@ import torch.nn.functional as F
 from torch.optim.lr_scheduler import CosineAnnealingLR, MultiplicativeLR
 
 from . import dist as rdist
-from .methods import train_rlvi
+from .methods import train_rlvi, train_rlvi_amp
 
 # per-dataset defaults of the reference (main.py:52-58, :92-97): epochs, batch, weight decay, lr
 DATASETS = {
@@ -173,22 +174,32 @@ def get_ratio_corrupted(mask, noise_mask):
     return clean_found, corr_found
 
 
+AMP_MODES = ("none", "bf16", "fp16")
+
 LOG_HEADER = "epoch:\ttime_ep\ttau\tfix\tclean,%\tcorr,%\ttrain_acc\tval_acc\ttest_acc\n"
 
 
 def run(n_train=16384, n_val=2048, n_test=2048, batch_size=1024, n_epoch=9, noise_rate=0.5,
         lr=0.1, momentum=0.9, wd=1e-3, seed=1, log_path=None, device="cuda", return_state=False,
-        dataset="mnist", noise_type="symmetric", schedule=True, train_fn=None, evaluate_fn=None):
+        dataset="mnist", noise_type="symmetric", schedule=True, train_fn=None, evaluate_fn=None, amp="none"):
     """main.py:run() for RLVI on synthetic data.  Returns the list of per-epoch log dicts (the first
     one is the reference's "epoch 0" line: the initial model's test accuracy).
 
     train_fn / evaluate_fn: the per-epoch training function (default: this package's train_rlvi)
     and the evaluation function -- the tests pass a plain-torch restatement to check the driver's
     bookkeeping.  Under an initialised torch.distributed group the loaders shard every batch over
-    the ranks and the model is wrapped in DistributedDataParallel."""
+    the ranks and the model is wrapped in DistributedDataParallel.
+
+    amp: "none" (fp32), "bf16" (training under torch.autocast with bf16, train_rlvi) or "fp16" (autocast with fp16
+    and a torch.amp.GradScaler, train_rlvi_amp -- train_fn, if given, is then called with the scaler as an eighth
+    argument).  Evaluation runs in fp32 either way."""
+    if amp not in AMP_MODES:
+        raise ValueError(f"amp must be one of {AMP_MODES}")
     cfg = DATASETS[dataset]
     device = torch.device(device)
-    train_fn = train_fn or train_rlvi
+    scaler = torch.amp.GradScaler(device.type) if amp == "fp16" else None
+    train_fn = train_fn or (train_rlvi_amp if scaler is not None else train_rlvi)
+    amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(amp)
     evaluate_fn = evaluate_fn or evaluate
     torch.manual_seed(seed)
     x, y, y_clean, noise_mask = synthetic_images(n_train + n_val + n_test, cfg["input_channel"],
@@ -231,8 +242,10 @@ def run(n_train=16384, n_val=2048, n_test=2048, batch_size=1024, n_epoch=9, nois
         net.train()
         t0 = time.time()
         lr_now = optimizer.param_groups[0]["lr"]
-        train_acc, threshold = train_fn(train_loader, net, optimizer, residuals,
-                                        sample_weights, overfit, threshold)         # main.py:277-280
+        with torch.autocast(device.type, dtype=amp_dtype, enabled=amp_dtype is not None):
+            extra = (scaler,) if scaler is not None else ()
+            train_acc, threshold = train_fn(train_loader, net, optimizer, residuals,
+                                            sample_weights, overfit, threshold, *extra)  # main.py:277-280
         # (under DDP every rank evaluates its own replica; BatchNorm's running statistics may differ by a
         #  rank's last batch, so the number that steers `overfit` is rank 0's on every rank)
         val_acc = rdist.rank0_value(evaluate_fn(val_loader, model, device))
@@ -277,6 +290,8 @@ def main(argv=None):
     ap.add_argument("--n_val", type=int, default=6000)
     ap.add_argument("--n_test", type=int, default=10000)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend under torchrun (nccl = RCCL)")
+    ap.add_argument("--amp", default="none", choices=AMP_MODES,
+                    help="mixed precision of the training step: bf16 autocast, or fp16 autocast with a GradScaler")
     a = ap.parse_args(argv)
     cfg = DATASETS[a.dataset]
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -291,7 +306,7 @@ def main(argv=None):
                batch_size=a.batch_size or cfg["batch_size"], n_epoch=a.n_epoch or cfg["n_epoch"],
                noise_rate=a.noise_rate, noise_type=a.noise_type, lr=a.lr_init or cfg["lr_init"],
                momentum=a.momentum, wd=a.wd if a.wd is not None else cfg["wd"], seed=a.seed, log_path=log,
-               device=f"cuda:{local}", dataset=a.dataset)
+               device=f"cuda:{local}", dataset=a.dataset, amp=a.amp)
     if world == 1 or torch.distributed.get_rank() == 0:
         for r in logs:
             print(r)

@@ -55,7 +55,19 @@ def train_rlvi(train_loader, model, optimizer,
     Opt-in for loaders that give every rank the SAME samples every epoch
     (rlvi_amd.dist.set_owner_sharding): nothing is exchanged or gathered at all -- the E-step and the
     threshold run sharded over the ranks' own samples, the kernels passing their totals through the
-    peers' inboxes -- and only the owned entries of residuals / weights are kept up to date on a rank."""
+    peers' inboxes -- and only the owned entries of residuals / weights are kept up to date on a rank.
+
+    Mixed precision: under torch.autocast the model's fp16 or bf16 logits go to the kernel as they are (no fp32
+    copy) and the gradient handed to autograd has their dtype.  fp16 training with loss scaling is
+    rlvi_amd.methods.train_rlvi_amp.train_rlvi_amp (this function owns the backward, so it has no place for a
+    GradScaler)."""
+    return _train_epoch(train_loader, model, optimizer, residuals, weights, overfit, threshold)
+
+
+def _train_epoch(train_loader, model, optimizer, residuals, weights, overfit, threshold, scaler=None):
+    """The epoch body of train_rlvi and train_rlvi_amp.  scaler: None (plain optimizer steps) or a
+    torch.amp.GradScaler, whose scale multiplies the gradient handed to autograd -- read on the device, no host
+    sync to get it -- before scaler.step(optimizer) and scaler.update()."""
     train_total = 0
     owner = rdist.owner_sharding() if rdist.world_size() > 1 else None
     ws = owner[1] if owner is not None else ops.workspace(weights.device, weights.shape[0], 0)
@@ -65,6 +77,9 @@ def train_rlvi(train_loader, model, optimizer,
     visited, sizes = [], []
     # the batch loop's launcher, validated once per epoch (vectors, workspace, stream)
     mstep = ops.MStepLoop(weights, residuals.detach(), ws)
+    scaled = scaler is not None and scaler.is_enabled()
+    autocast = torch.is_autocast_enabled(weights.device.type)
+    one = torch.ones((), dtype=torch.float32, device=weights.device) if scaled else None
 
     for (images, labels, indexes) in train_loader:
         images = images.to(weights.device, non_blocking=True)
@@ -82,12 +97,24 @@ def train_rlvi(train_loader, model, optimizer,
         # reference :85,:89-94 and the backward of :96 in ONE fused launch over the logits:
         # top-1, per-sample CE, residuals[indexes] = loss, weights[indexes] gather, weighted
         # mean and d(loss)/d(logits); the batch scalars accumulate on the device
-        grad = mstep(logits, labels, indexes, inv_scale)
+        if scaled:
+            # the loss scale as a device tensor: scaler.scale() is a device multiply, get_scale() would sync
+            grad = mstep(logits, labels, indexes, inv_scale, grad_scale=scaler.scale(one))
+        else:
+            grad = mstep(logits, labels, indexes, inv_scale)
         train_total += 1
 
         optimizer.zero_grad()
         logits.backward(grad)          # == loss.backward() of the reference (:96)
-        optimizer.step()
+        if scaler is not None:
+            scaler.step(optimizer)     # unscales, skips the step when a gradient is not finite
+            scaler.update()
+        else:
+            optimizer.step()
+        if autocast:
+            # an epoch inside ONE autocast region: its cache still holds the low-precision copies of the weights
+            # the step has just changed -- the next batch must cast them anew
+            torch.clear_autocast_cache()
 
     if world > 1:
         if not rdist.ragged():

@@ -117,8 +117,37 @@ def workspace(device, n=0, b=0):
     return ws
 
 
+_NATIVE = (torch.float32, torch.bfloat16, torch.float16)      # logit dtypes with entries of their own
+
+
+def _check_grad_scale(grad_scale, device):
+    """A loss scale (torch.amp.GradScaler's scale tensor): one fp32 value on the logits' device, read there."""
+    if grad_scale is None:
+        return None
+    if not torch.is_tensor(grad_scale) or grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 \
+            or grad_scale.device != device:
+        raise ValueError("grad_scale must be a one-element fp32 tensor on the logits' device")
+    return grad_scale
+
+
+def _mstep_call(L, logits, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad, out, ws):
+    """The dtype's C entry.  fp16 reads the loss scale on the device (one rounding of the scaled gradient); fp32 and
+    bf16 have no such argument: their gradient is multiplied by the scale tensor afterwards (stock AMP semantics)."""
+    args = (_ptr(logits), logits.stride(0), _ptr(labels), _ptr(idx), _ptr(weights), _ptr(residuals), N, B, C,
+            float(inv_scale))
+    tail = (_ptr(grad), grad.stride(0) if grad is not None else 0, _ptr(out), ws.ptr, _stream_ptr())
+    if logits.dtype == torch.float16:
+        rc = L.rlvi_mstep_fwd_bwd_f16(*args, _ptr(grad_scale), *tail)
+    else:
+        fn = L.rlvi_mstep_fwd_bwd_f32 if logits.dtype == torch.float32 else L.rlvi_mstep_fwd_bwd_bf16
+        rc = fn(*args, *tail)
+        if rc == 0 and grad is not None and grad_scale is not None:
+            grad.mul_(grad_scale)
+    return rc
+
+
 def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_grad=True,
-                  out=None, grad=None, ws=None, accumulate=False):
+                  out=None, grad=None, ws=None, accumulate=False, grad_scale=None):
     """One mini-batch of the M-step (train_rlvi.py:85-96 without model/optimizer).
 
     Scatters the per-sample NLL into `residuals[idx]`, gathers the lagged pi from
@@ -126,13 +155,16 @@ def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_
     {weighted mean loss, top-1 %, sum pi*l, hits} and grad = dL/dlogits (or None).
     accumulate=True: ONE launch, no scalars now (out is None): the per-batch sums pile up in the
     workspace until `epoch_end` / `mstep_reduce` collects them.
+    fp32, bf16 and fp16 logits run natively; the gradient has the logits' dtype.  grad_scale: an optional
+    one-element fp32 device tensor (a GradScaler's scale) that multiplies the gradient only -- read by the kernel
+    for fp16 logits, no host sync either way.
     """
     L = _lib.load()
     _require_gpu(logits, labels, idx, weights, residuals)
     if logits.dim() != 2:
         raise ValueError("logits must be [B, C]")
     B, C = logits.shape
-    if logits.dtype not in (torch.float32, torch.bfloat16):
+    if logits.dtype not in _NATIVE:
         logits = logits.float()
     if logits.stride(1) != 1:
         logits = logits.contiguous()
@@ -153,12 +185,10 @@ def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_
         grad = torch.empty((B, C), dtype=logits.dtype, device=logits.device)
     if not want_grad:
         grad = None
+    grad_scale = _check_grad_scale(grad_scale, logits.device)
     ws = ws or workspace(logits.device, N, B)
-    fn = L.rlvi_mstep_fwd_bwd_f32 if logits.dtype == torch.float32 else L.rlvi_mstep_fwd_bwd_bf16
-    rc = fn(_ptr(logits), logits.stride(0), _ptr(labels), _ptr(idx), _ptr(weights),
-            _ptr(residuals), N, B, C, float(inv_scale if inv_scale is not None else 1.0 / B),
-            _ptr(grad), grad.stride(0) if grad is not None else 0, _ptr(out), ws.ptr,
-            _stream_ptr())
+    rc = _mstep_call(L, logits, labels, idx, weights, residuals, N, B, C,
+                     inv_scale if inv_scale is not None else 1.0 / B, grad_scale, grad, out, ws)
     _lib.check(rc, "rlvi_mstep_fwd_bwd")
     return out, grad
 
@@ -182,8 +212,13 @@ class MStepLoop:
     (train_rlvi makes one per epoch), so a batch costs a handful of data_ptr() reads, one cached gradient
     buffer per batch shape and the foreign call -- the generic wrapper's ~10 checks, dict look-ups,
     c_void_p objects and current-stream query are what a 4-microsecond kernel at 4096 x 10 was waiting for.
-    A batch that does not look like the validated form (strided / non-fp32-bf16 logits, labels or indexes
-    that are not contiguous int64 device tensors) takes the generic, fully checked path.
+    A batch that does not look like the validated form (strided logits or logits that are not fp32 / bf16 / fp16,
+    labels or indexes that are not contiguous int64 device tensors, a loss scale that is not a one-element fp32
+    tensor on the loop's device) takes the generic, fully checked path.
+
+    grad_scale (optional): a GradScaler's scale tensor; the gradient comes back multiplied by it -- fp16 logits
+    read it inside the kernel (one rounding, an overflow becomes inf), fp32 / bf16 multiply the buffer in place.
+    The loss, the residuals and the epoch's records never see it.
 
     The returned gradient buffer is REUSED by the next batch of the same shape: consume it
     (`logits.backward(grad)`) before the next call, as train_rlvi does."""
@@ -201,34 +236,44 @@ class MStepLoop:
         self.ws = ws or workspace(weights.device, self.N, 0)
         self._w, self._r, self._wsp = weights.data_ptr(), residuals.data_ptr(), self.ws.buf.data_ptr()
         self._stream = torch.cuda.current_stream(weights.device).cuda_stream
-        self._f32, self._bf16 = L.rlvi_mstep_fwd_bwd_f32, L.rlvi_mstep_fwd_bwd_bf16
+        self._f32, self._bf16, self._f16 = L.rlvi_mstep_fwd_bwd_f32, L.rlvi_mstep_fwd_bwd_bf16, L.rlvi_mstep_fwd_bwd_f16
         self._grads = {}
         self._dev = weights.device
         self._devidx = weights.device.index if weights.device.index is not None else torch.cuda.current_device()
 
-    def __call__(self, logits, labels, idx, inv_scale=None):
+    def __call__(self, logits, labels, idx, inv_scale=None, grad_scale=None):
         dt = logits.dtype
         # the validated form, on the device and the stream the loop was made on; anything else -- strided or
         # other-typed logits, no index vector, a tensor on another device, a caller that has switched streams
         # inside the epoch -- takes the generic, fully checked wrapper (which launches on the CURRENT stream)
-        if not (idx is not None and (dt is torch.float32 or dt is torch.bfloat16) and logits.dim() == 2
+        if not (idx is not None and (dt is torch.float32 or dt is torch.bfloat16 or dt is torch.float16)
+                and logits.dim() == 2
                 and logits.is_contiguous() and labels.dtype is torch.int64 and idx.dtype is torch.int64
                 and labels.is_contiguous() and idx.is_contiguous()
                 and logits.device == self._dev and labels.is_cuda and idx.is_cuda
+                and (grad_scale is None or (grad_scale.dtype is torch.float32 and grad_scale.numel() == 1
+                                            and grad_scale.device == self._dev))
                 and _raw_stream(self._devidx) == self._stream):
             _require_gpu(logits, labels, idx)
             _, grad = mstep_fwd_bwd(logits.detach(), labels, idx, self.weights, self.residuals,
-                                    inv_scale=inv_scale, accumulate=True, ws=self.ws)
+                                    inv_scale=inv_scale, accumulate=True, ws=self.ws, grad_scale=grad_scale)
             return grad
         B, C = logits.shape
         key = (B, C, dt)
         grad = self._grads.get(key)
         if grad is None:
             grad = self._grads[key] = torch.empty((B, C), dtype=dt, device=self._dev)
-        rc = (self._f32 if dt is torch.float32 else self._bf16)(
-            logits.data_ptr(), C, labels.data_ptr(), idx.data_ptr(), self._w, self._r, self.N, B, C,
-            float(inv_scale) if inv_scale is not None else 1.0 / B, grad.data_ptr(), C, None, self._wsp,
-            self._stream)
+        s = float(inv_scale) if inv_scale is not None else 1.0 / B
+        if dt is torch.float16:
+            rc = self._f16(logits.data_ptr(), C, labels.data_ptr(), idx.data_ptr(), self._w, self._r, self.N, B, C, s,
+                           grad_scale.data_ptr() if grad_scale is not None else None, grad.data_ptr(), C, None,
+                           self._wsp, self._stream)
+        else:
+            rc = (self._f32 if dt is torch.float32 else self._bf16)(
+                logits.data_ptr(), C, labels.data_ptr(), idx.data_ptr(), self._w, self._r, self.N, B, C, s,
+                grad.data_ptr(), C, None, self._wsp, self._stream)
+            if grad_scale is not None and not rc:
+                grad.mul_(grad_scale)
         if rc:
             _lib.check(rc, "rlvi_mstep_fwd_bwd")
         return grad
@@ -256,7 +301,7 @@ def evaluate_batch(logits, labels, out=None, ws=None):
     CE, hits}."""
     L = _lib.load()
     _require_gpu(logits, labels)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
+    if logits.dtype not in _NATIVE:
         logits = logits.float()
     if logits.stride(1) != 1:
         logits = logits.contiguous()
@@ -265,9 +310,8 @@ def evaluate_batch(logits, labels, out=None, ws=None):
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=logits.device)
     ws = ws or workspace(logits.device, B, B)
-    fn = L.rlvi_mstep_fwd_bwd_f32 if logits.dtype == torch.float32 else L.rlvi_mstep_fwd_bwd_bf16
-    _lib.check(fn(_ptr(logits), logits.stride(0), _ptr(labels), None, None, None, B, B, C, 1.0 / B,
-                  None, 0, _ptr(out), ws.ptr, _stream_ptr()), "rlvi_mstep_fwd_bwd (evaluation form)")
+    _lib.check(_mstep_call(L, logits, labels, None, None, None, B, B, C, 1.0 / B, None, None, out, ws),
+               "rlvi_mstep_fwd_bwd (evaluation form)")
     return out
 
 
@@ -583,7 +627,7 @@ def topk_hits(logits, labels, ks, out=None):
         raise ValueError("between one and eight values of k per call")
     if max(ks) > C or min(ks) < 1:
         raise RuntimeError("selected index k out of range")
-    if logits.dtype not in (torch.float32, torch.bfloat16):
+    if logits.dtype not in _NATIVE:
         logits = logits.float()
     if logits.stride(1) != 1:
         logits = logits.contiguous()
@@ -592,7 +636,8 @@ def topk_hits(logits, labels, ks, out=None):
     if out is None:
         out = torch.empty(len(ks), dtype=torch.int32, device=logits.device)
     karr = (ctypes.c_int32 * len(ks))(*ks)
-    fn = L.rlvi_topk_hits_f32 if logits.dtype == torch.float32 else L.rlvi_topk_hits_bf16
+    fn = {torch.float32: L.rlvi_topk_hits_f32, torch.bfloat16: L.rlvi_topk_hits_bf16,
+          torch.float16: L.rlvi_topk_hits_f16}[logits.dtype]
     _lib.check(fn(_ptr(logits), logits.stride(0), _ptr(labels), B, C, karr, len(ks), _ptr(out), _stream_ptr()),
                "rlvi_topk_hits")
     return out
