@@ -18,6 +18,8 @@ Golden sets:
   G7 estimators   mean, pca, covariance            standard-learning/rlvi.py:23-65,:111-144
   G8 small-loss   usdnl.loss_fn, loss_coteaching   train_usdnl.py:16-27, train_coteaching.py:17-35
   G9 top-1 ties   evaluate() on tied maxima        deep-learning/utils.py:48-62
+  G10 precision@k accuracy(topk=(1, 3, 5))         deep-learning/utils.py:65-79
+  G11 near-ties   update_sample_weights' count     train_rlvi.py:26-38 (recipes of synth.near_tie)
 """
 import argparse
 import os
@@ -56,7 +58,7 @@ def ref_deep(ref):
     return sys.modules["methods.train_rlvi"]
 
 
-def run_estep_traced(m, residuals, weights):
+def run_estep_traced(m, residuals, weights, **kw):
     """Call the reference E-step, recording `error` of every iteration."""
     import torch
     errs = []
@@ -68,7 +70,7 @@ def run_estep_traced(m, residuals, weights):
         return v
     torch.norm = spy
     try:
-        m.update_sample_weights(residuals, weights)
+        m.update_sample_weights(residuals, weights, **kw)
     finally:
         torch.norm = orig
     return np.array(errs, np.float32)
@@ -492,7 +494,83 @@ def gen_g10(ref):
     save("g10_topk", **out)
 
 
-GROUPS = {"g10": gen_g10, "g9": gen_g9, "g7": gen_g7, "g8": gen_g8, "g12": gen_g1_g2, "g3": gen_g3, "g4": gen_g4, "g5": gen_g5, "g6": gen_g6}
+# G11: (kind, N, seed, tol, maxiter, stop test k, margins); every margin on both sides of tol.  The entries
+# cover the six kinds, stop tests 0, 1, a middle one and maxiter - 1, tol 1e-2 / 1e-3 / 1e-4, maxiter 40 / 64,
+# and the sizes that take each E-step form (N < 64 and maxiter > 64: the iterative kernel)
+G11_MARGINS = (3e-2, 1e-2, 3e-3, 1e-3, 3e-4, 1e-4)
+G11_ENTRIES = (
+    ("narrow", 4096, 11, 1e-3, 40, 1, G11_MARGINS),       # spread ~7e-4: r/|h| in the hundreds
+    ("narrow", 4096, 12, 1e-3, 40, 20, G11_MARGINS),      # the trajectory's slow descent
+    ("narrow", 1000, 13, 1e-2, 64, 63, G11_MARGINS),
+    ("narrow", 65536, 31, 1e-2, 64, 30, G11_MARGINS),
+    ("narrow", 4096, 32, 1e-2, 40, 0, G11_MARGINS),       # the caller's pi
+    ("bimodal", 65536, 21, 1e-3, 40, 20, G11_MARGINS),
+    ("exp", 262144, 22, 1e-3, 40, 20, G11_MARGINS),
+    ("zeros10", 1000, 23, 1e-2, 40, 20, G11_MARGINS),
+    ("ce", 4096, 24, 1e-2, 40, 39, G11_MARGINS),
+    ("heavy", 256, 25, 1e-4, 64, 63, G11_MARGINS),
+    ("bimodal", 64, 26, 1e-3, 40, 20, G11_MARGINS),
+    ("exp", 65, 27, 1e-2, 40, 1, G11_MARGINS),
+    ("narrow", 2097152, 28, 1e-2, 40, 1, (1e-2, 1e-3)),
+    ("bimodal", 40, 29, 1e-3, 40, 20, G11_MARGINS),       # N < 64: iterative kernel
+    ("bimodal", 4096, 30, 1e-3, 80, 20, G11_MARGINS),     # maxiter > 64: iterative kernel
+)
+
+
+def save_deterministic(name, **kw):
+    """np.savez_compressed with fixed zip timestamps and no version strings: running the generator again
+    writes the same bytes."""
+    import io
+    import zipfile
+    path = os.path.join(OUT, name + ".npz")
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key in sorted(kw):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(kw[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue())
+    print(f"wrote {path} ({os.path.getsize(path)/1024:.1f} KiB)")
+
+
+def gen_g11(ref):
+    """Near-ties of the E-step's stop decision: the recipe of every case (synth.near_tie_vectors(kind, N,
+    seed, k, knob), the knob found by bisection in fp64) with the REFERENCE's own count and error trace on
+    the rebuilt fp32 vectors (the margins reached are recomputed by the tests: synth.estep_trace64)."""
+    import torch
+    torch.set_num_threads(1)                 # (the reference's reductions: one summation order)
+    m = ref_deep(ref)
+    keys, kinds, recipe, reals, iters, errs_all = [], [], [], [], [], []
+    for e, (kind, N, seed, tol, maxiter, k, margins) in enumerate(G11_ENTRIES):
+        bracket = None
+        for margin in margins:
+            for side in (1, -1):
+                d = synth.near_tie(kind, N, seed, tol, maxiter, k, margin, side, bracket=bracket)
+                bracket = d["bracket"]
+                reached = d["margins"][k] if k < len(d["margins"]) else np.nan
+                assert abs(reached - side * margin) <= 0.01 * margin, (kind, N, k, margin, side, reached)
+                r, w = synth.near_tie_vectors(kind, N, seed, k, d["knob"])
+                assert np.array_equal(r, d["residuals"]) and np.array_equal(w, d["weights"])
+                rt, wt = torch.from_numpy(r.copy()), torch.from_numpy(w.copy())
+                errs = run_estep_traced(m, rt, wt, tol=tol, maxiter=maxiter)
+                keys.append(f"e{e:02d}_{kind}_{N}_k{k}_m{margin:.0e}_{'p' if side > 0 else 'm'}")
+                kinds.append(kind)
+                recipe.append([e, N, seed, maxiter, k, side])
+                reals.append([tol, margin, d["knob"]])
+                iters.append(len(errs))
+                row = np.zeros(max(x[4] for x in G11_ENTRIES), np.float32)
+                row[:len(errs)] = errs
+                errs_all.append(row)
+        print(f"g11 entry {e}: {kind} N={N} k={k} done", flush=True)
+    # one row per case: recipe = (entry, N, seed, maxiter, k, side), real = (tol, margin, knob), the
+    # reference's count and its errors (zero-padded)
+    out = dict(cases=np.array(keys), kind=np.array(kinds), recipe=np.array(recipe, np.int64),
+               real=np.array(reals, np.float64), ref_iters=np.array(iters, np.int64), ref_errs=np.stack(errs_all))
+    save_deterministic("g11_near_ties", **out)
+
+
+GROUPS = {"g11": gen_g11, "g10": gen_g10, "g9": gen_g9, "g7": gen_g7, "g8": gen_g8, "g12": gen_g1_g2, "g3": gen_g3, "g4": gen_g4, "g5": gen_g5, "g6": gen_g6}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
