@@ -268,6 +268,59 @@ int rlvi_truncate_f32(float *weights, int64_t N, const float *thr, uint8_t *mask
 int rlvi_select_smallest_f32(const float *loss, int64_t n, int64_t k, float *mask_w, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * JoCoR's joint loss of two networks, forward and backward.  Replaces loss_jocor(y_1, y_2, t, forget_rate, ind,
+ * co_lambda) of deep-learning/methods/train_jocor.py:29-43 -- F.cross_entropy of both blocks (:30-31),
+ * kl_loss_compute both ways (:17-26, :33-34), the .cpu() and np.argsort (:34-36), the gather and the mean
+ * (:37-42) -- and the backward of all of it into both blocks, reached from loss_1.backward() (:71).
+ * As the reference runs it: kl_loss_compute(..., reduce='none') takes its `if reduce:` branch (the string is
+ * truthy), so K_qp = mean_b KL(q_b || p_b) and K_pq = mean_b KL(p_b || q_b) are batch means, one scalar each, and
+ *     loss_pick_i = ((0.9 CE1_i + 0.9 CE2_i) + lambda K_qp) + lambda K_pq      (fp32, the reference's rounding order;
+ *                                                                               0.9 stands for 1 - lambda)
+ * with p = softmax(logits1_i), q = softmax(logits2_i).  The k smallest loss_pick are kept (equal values in index
+ * order, NaN last; np.argsort's order among equal values is unpinned) and L = their mean; k = 0 gives L = NaN.
+ *
+ * Forward, two launches (pass 1 over both blocks, then the selection in one workgroup), no host round trip:
+ *   logits1, logits2  [B, C] row-major, leading dimensions ld1, ld2 (elements)
+ *   labels            [B] int64; a label outside [0, C) sets RLVI_ST_RANGE, its row's cross-entropies are NaN
+ *   k                 int((1 - forget_rate) * B) of the caller (:38-39); k >= B keeps every row
+ *   co_lambda         lambda (0.1 in the reference)
+ *   loss_pick  [B] fp32 out: every row's loss_pick;   sel [B] fp32 out: 1.0 for the kept rows, else 0.0
+ *   out        [4] fp32 out: { L, K_qp, K_pq, 100 * (top-1 hits of logits1) / B } (train_jocor.py:58-60)
+ *   ws         a workspace (its records of calls with `out`; any size)
+ * Backward, one launch: grad1, grad2 [B, C] (ldg1, ldg2; either may be NULL) in the logits' dtype, rounded once:
+ *   grad1 = g * ( sel_i (1-lambda)/k (p - e_y) + lambda/B ((p - q) + p (log p - log q - KL(p||q)_i)) )
+ *   grad2 = g * ( sel_i (1-lambda)/k (q - e_y) + lambda/B ((q - p) + q (log q - log p - KL(q||p)_i)) )
+ * every row, kept or not, receives the KL term; k = 0: both gradients are zero (nothing flows back from a mean of
+ * nothing).  g = (*grad_out) * (*grad_scale): DEVICE pointers to one fp32 value each (autograd's upstream gradient,
+ * a GradScaler's scale), read by the kernel; NULL stands for 1.  `sel`, `labels`, k and co_lambda must be those of
+ * the forward call.
+ * bf16 / fp16 entries: the logits and gradients are bfloat16 / IEEE binary16 (16-bit patterns), arithmetic is
+ * fp32 on the exactly widened values; the gradients are rounded to nearest even (fp16: subnormals kept, +-inf on
+ * overflow).  Any C up to 2^20 (RLVI_E_LIMIT beyond); rows of more than 1024 elements (fewer with an unaligned
+ * pitch) take a slower form that sweeps each row from memory.  B < 2^31.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_jocor_fwd_f32(const float *logits1, int64_t ld1, const float *logits2, int64_t ld2, const int64_t *labels,
+                       int64_t B, int64_t C, int64_t k, float co_lambda, float *loss_pick, float *sel, float *out,
+                       void *ws, void *stream);
+int rlvi_jocor_fwd_bf16(const uint16_t *logits1, int64_t ld1, const uint16_t *logits2, int64_t ld2,
+                        const int64_t *labels, int64_t B, int64_t C, int64_t k, float co_lambda, float *loss_pick,
+                        float *sel, float *out, void *ws, void *stream);
+int rlvi_jocor_fwd_f16(const uint16_t *logits1, int64_t ld1, const uint16_t *logits2, int64_t ld2,
+                       const int64_t *labels, int64_t B, int64_t C, int64_t k, float co_lambda, float *loss_pick,
+                       float *sel, float *out, void *ws, void *stream);
+int rlvi_jocor_bwd_f32(const float *logits1, int64_t ld1, const float *logits2, int64_t ld2, const int64_t *labels,
+                       const float *sel, int64_t B, int64_t C, int64_t k, float co_lambda, const float *grad_out,
+                       const float *grad_scale, float *grad1, int64_t ldg1, float *grad2, int64_t ldg2, void *stream);
+int rlvi_jocor_bwd_bf16(const uint16_t *logits1, int64_t ld1, const uint16_t *logits2, int64_t ld2,
+                        const int64_t *labels, const float *sel, int64_t B, int64_t C, int64_t k, float co_lambda,
+                        const float *grad_out, const float *grad_scale, uint16_t *grad1, int64_t ldg1,
+                        uint16_t *grad2, int64_t ldg2, void *stream);
+int rlvi_jocor_bwd_f16(const uint16_t *logits1, int64_t ld1, const uint16_t *logits2, int64_t ld2,
+                       const int64_t *labels, const float *sel, int64_t B, int64_t C, int64_t k, float co_lambda,
+                       const float *grad_out, const float *grad_scale, uint16_t *grad1, int64_t ldg1,
+                       uint16_t *grad2, int64_t ldg2, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * precision@k.  Replaces accuracy(logit, target, topk) of deep-learning/utils.py:65-79 (softmax :67, torch.topk
  * :70, eq :72, the per-k counts :76-77): hits[j] = number of rows whose label is among the ks[j]
  * largest logits of its row, j < nk <= 8.  train_rlvi keeps only precision@1 (train_rlvi.py:85), which the

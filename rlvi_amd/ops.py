@@ -675,3 +675,110 @@ def selected_cross_entropy(logits, labels, mask, inv_scale):
 def weighted_cross_entropy(logits, labels, idx, weights, residuals, inv_scale=None):
     """Autograd entry: returns (loss 0-dim tensor, out[4])."""
     return _WeightedCE.apply(logits, labels, idx, weights, residuals, inv_scale)
+
+
+_JOCOR_ENTRIES = {torch.float32: ("rlvi_jocor_fwd_f32", "rlvi_jocor_bwd_f32"),
+                  torch.bfloat16: ("rlvi_jocor_fwd_bf16", "rlvi_jocor_bwd_bf16"),
+                  torch.float16: ("rlvi_jocor_fwd_f16", "rlvi_jocor_bwd_f16")}
+
+
+def _jocor_blocks(logits1, logits2, labels):
+    """Both blocks in one native dtype (their own if they share one, else fp32), unit column stride; int64 labels."""
+    _require_gpu(logits1, logits2, labels)
+    if logits1.dim() != 2 or logits1.shape != logits2.shape:
+        raise ValueError("logits1 and logits2 must both be [B, C]")
+    if labels.dim() != 1 or labels.shape[0] != logits1.shape[0]:
+        raise ValueError("labels must be a [B] vector")
+    if logits1.dtype != logits2.dtype or logits1.dtype not in _NATIVE:
+        logits1, logits2 = logits1.float(), logits2.float()
+    if logits1.stride(1) != 1:
+        logits1 = logits1.contiguous()
+    if logits2.stride(1) != 1:
+        logits2 = logits2.contiguous()
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        labels = labels.to(torch.int64).contiguous()
+    return logits1, logits2, labels
+
+
+def jocor_forward(logits1, logits2, labels, k, co_lambda=0.1, out=None, ws=None):
+    """Forward of loss_jocor (train_jocor.py:29-43) without autograd: pass 1 + selection.  Returns (out, loss_pick,
+    sel): out fp32[4] = {L, K_qp, K_pq, top-1 % of logits1}, loss_pick [B] and the 0/1 selection sel [B], all on the
+    device (no host synchronisation).  Blocks as _jocor_blocks leaves them; see include/rlvi_hip.h."""
+    L = _lib.load()
+    B, C = logits1.shape
+    dev = logits1.device
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    loss_pick = torch.empty(B, dtype=torch.float32, device=dev)
+    sel = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = ws or workspace(dev)
+    fn = getattr(L, _JOCOR_ENTRIES[logits1.dtype][0])
+    _lib.check(fn(_ptr(logits1), logits1.stride(0), _ptr(logits2), logits2.stride(0), _ptr(labels), B, C, int(k),
+                  float(co_lambda), _ptr(loss_pick), _ptr(sel), _ptr(out), ws.ptr, _stream_ptr()), "rlvi_jocor_fwd")
+    return out, loss_pick, sel
+
+
+def jocor_backward(logits1, logits2, labels, sel, k, co_lambda=0.1, grad_out=None, grad_scale=None,
+                   want1=True, want2=True):
+    """Backward of loss_jocor into both blocks (pass 2): (grad1, grad2) in the logits' dtype, None where not wanted.
+    grad_out / grad_scale: one-element fp32 device tensors (upstream gradient, loss scale) read by the kernel."""
+    L = _lib.load()
+    B, C = logits1.shape
+    dev = logits1.device
+    for t in (grad_out, grad_scale):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != dev):
+            raise ValueError("grad_out / grad_scale must be one-element fp32 tensors on the logits' device")
+    g1 = torch.empty((B, C), dtype=logits1.dtype, device=dev) if want1 else None
+    g2 = torch.empty((B, C), dtype=logits1.dtype, device=dev) if want2 else None
+    fn = getattr(L, _JOCOR_ENTRIES[logits1.dtype][1])
+    _lib.check(fn(_ptr(logits1), logits1.stride(0), _ptr(logits2), logits2.stride(0), _ptr(labels), _ptr(sel), B, C,
+                  int(k), float(co_lambda), _ptr(grad_out), _ptr(grad_scale), _ptr(g1), C if want1 else 0, _ptr(g2),
+                  C if want2 else 0, _stream_ptr()), "rlvi_jocor_bwd")
+    return g1, g2
+
+
+class _JoCoRLoss(torch.autograd.Function):
+    """L = mean of the k smallest loss_pick (train_jocor.py:29-43); backward = pass 2 with autograd's upstream gradient
+    read on the device (a GradScaler's scale arrives the same way: scaler.scale(L) multiplies it in)."""
+
+    @staticmethod
+    def forward(ctx, logits1, logits2, labels, k, co_lambda, ws, out):
+        out, _, sel = jocor_forward(logits1.detach(), logits2.detach(), labels, k, co_lambda, out=out, ws=ws)
+        ctx.save_for_backward(logits1, logits2, labels, sel)
+        ctx.k, ctx.co_lambda = k, co_lambda
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        z1, z2, labels, sel = ctx.saved_tensors
+        g = g.detach()
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.to(torch.float32).contiguous()
+        g1, g2 = jocor_backward(z1.detach(), z2.detach(), labels, sel, ctx.k, ctx.co_lambda, grad_out=g,
+                                want1=ctx.needs_input_grad[0], want2=ctx.needs_input_grad[1])
+        return g1, g2, None, None, None, None, None
+
+
+def jocor_num_remember(forget_rate, B):
+    """k of train_jocor.py:38-40: int((1 - forget_rate) * B) as ind_sorted[:k] takes it (a negative k drops |k|)."""
+    k = int((1 - forget_rate) * B)
+    return max(B + k, 0) if k < 0 else min(k, B)
+
+
+def jocor_loss(logits1, logits2, labels, forget_rate, co_lambda=0.1, ws=None, out=None, check=True):
+    """loss_jocor (deep-learning/methods/train_jocor.py:29-43) on the device: a 0-dim fp32 tensor L with gradients
+    for both blocks.  The reference's loss is a CPU tensor (its .cpu() at :34, then argsort on the host); this one
+    stays on the logits' device -- train_jocor only calls .backward() on it.  The KL terms are the reference's batch
+    means (kl_loss_compute's `if reduce:` with reduce='none', :23), so every row gets the KL gradient.
+    Both blocks run in their own dtype if they share one of fp32 / bf16 / fp16, else both in fp32; the gradients come
+    back in the inputs' dtypes.  Works under torch.autocast and with a GradScaler (scaler.scale(L).backward()).
+    out: optional fp32[4] device tensor that receives {L, K_qp, K_pq, top-1 % of logits1}.  check=True reads the
+    device status (one 4-byte copy, a sync as the reference's .cpu() is) and raises on a label out of range; a
+    training loop passes False and reads the status once at its end."""
+    z1, z2, labels = _jocor_blocks(logits1, logits2, labels)
+    k = jocor_num_remember(forget_rate, z1.shape[0])
+    ws = ws or workspace(z1.device)
+    loss = _JoCoRLoss.apply(z1, z2, labels, k, float(co_lambda), ws, out)
+    if check:
+        ws.raise_on_status("jocor_loss")
+    return loss

@@ -206,3 +206,22 @@ def heavy_tail_cloud(size=200, eps=0.2, nu=1.5, seed=0, corr=0.8):
     u = rng.chisquare(df=nu, size=n2) / nu
     s2 = (root @ rng.normal(size=(2, n2))) / np.sqrt(u[None, :])
     return np.hstack([s1, s2]).T
+
+
+def jocor_loop_inputs(seed=1212, N=256, D=16, C=10, noise=0.3):
+    """Inputs of the three-epoch JoCoR run of golden set G12: features X [N, D] fp32, labels [N] int64 of a
+    linear teacher with `noise` of them replaced at random."""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((N, D)).astype(np.float32)
+    W = rng.standard_normal((D, C))
+    labels = np.argmax(X.astype(np.float64) @ W, axis=1).astype(np.int64)
+    flip = rng.random(N) < noise
+    labels[flip] = rng.integers(0, C, int(flip.sum()))
+    return X, labels
+
+
+def jocor_rate_schedule(forget_rate, n_epoch, num_gradual, exponent=1.0):
+    """rate_schedule of deep-learning/main.py:172-180."""
+    rs = np.ones(n_epoch) * forget_rate
+    rs[:num_gradual] = np.linspace(0, forget_rate ** exponent, num_gradual)
+    return rs
