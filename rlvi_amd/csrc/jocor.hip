@@ -17,80 +17,19 @@
 //     hits} per workgroup (no atomics: fixed-order sums);
 //   selection (jocor_select_kernel, one workgroup): reduces the records in a fixed order, forms every loss_pick_i
 //     with the reference's fp32 rounding order ((a_i + lambda K_qp) + lambda K_pq), takes the k smallest by the
-//     radix select of select.hip (equal values in index order), writes the 0/1 selection, loss_pick and
+//     radix select of rlvi_select.h (equal values in index order), writes the 0/1 selection, loss_pick and
 //     out = {L, K_qp, K_pq, top-1 % of model 1};
 //   pass 2 (jocor_grad_kernel): re-reads both blocks and writes both gradients in the logits' dtype (one rounding,
 //     nearest even), scaled by the upstream gradient and an optional loss scale read on the device once per wave.
 // A row of at most 16 G elements lives in the registers of a group of G lanes (V-element vectors); longer rows
 // take a wave per row that sweeps the row from memory (the second and later sweeps are cache hits).
-#include "rlvi_common.h"
+#include "rlvi_select.h"
 
 namespace rlvi {
 
 constexpr int JC_THREADS = 256;
 constexpr int JC_WAVES = JC_THREADS / WAVE;
 constexpr int JC_ELEMS = 16;                 // elements per lane and block of the register form (JC_ELEMS / V vectors)
-constexpr int JC_SEL_BLOCK = 1024;
-constexpr int JC_SEL_NW = JC_SEL_BLOCK / WAVE;
-constexpr int JC_SEL_U = 8;                  // loads in flight per thread in the selection's sweeps
-
-// V consecutive elements <-> fp32 (2-byte formats widened / narrowed through Half<T>)
-template <typename T, int V>
-struct JVec {
-    static __device__ __forceinline__ void load(const T *p, float (&v)[V]) {
-        if constexpr (V == 1) {
-            v[0] = Half<T>::widen(*reinterpret_cast<const uint16_t *>(p));
-        } else if constexpr (V == 2) {
-            const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
-            v[0] = Half<T>::lo(w); v[1] = Half<T>::hi(w);
-        } else {
-            static_assert(V == 8, "2-byte vectors of 1, 2 or 8 elements");
-            const uint4 t = *reinterpret_cast<const uint4 *>(p);
-            const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { v[2 * i] = Half<T>::lo(w[i]); v[2 * i + 1] = Half<T>::hi(w[i]); }
-        }
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[V]) {
-        if constexpr (V == 1) {
-            *reinterpret_cast<uint16_t *>(p) = Half<T>::narrow(v[0]);
-        } else if constexpr (V == 2) {
-            *reinterpret_cast<uint32_t *>(p) = Half<T>::narrow2(v[0], v[1]);
-        } else {
-            uint32_t w[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = Half<T>::narrow2(v[2 * i], v[2 * i + 1]);
-            *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-};
-template <int V>
-struct JVec<float, V> {
-    static __device__ __forceinline__ void load(const float *p, float (&v)[V]) {
-        if constexpr (V == 1) {
-            v[0] = *p;
-        } else if constexpr (V == 2) {
-            const float2 t = *reinterpret_cast<const float2 *>(p);
-            v[0] = t.x; v[1] = t.y;
-        } else {
-            static_assert(V == 4, "fp32 vectors of 1, 2 or 4 elements");
-            const float4 t = *reinterpret_cast<const float4 *>(p);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        }
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[V]) {
-        if constexpr (V == 1) *p = v[0];
-        else if constexpr (V == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-        else *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-};
-
-// g * (*grad_scale): the factor of both gradients, wave-uniform (one read per wave, kept in an SGPR)
-__device__ __forceinline__ float jc_gain(const float *grad_out, const float *grad_scale) {
-    float g = grad_out != nullptr ? *grad_out : 1.0f;
-    if (grad_scale != nullptr) g *= *grad_scale;
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g)));
-}
 
 // One row in the registers of G lanes: lane g holds the vectors k*G + g, k < kact <= JC_KMAX.  After
 // stats(), d1 / d2 hold z - max (dead slots -inf) and the row's log-sum-exp parts and KL terms are set.
@@ -110,8 +49,8 @@ struct RegRow {
             const int col = (k * G + g) * V;
             live[k] = k < kact && col < C;
             const int c = live[k] ? col : g * V < C ? g * V : 0;     // dead slots re-read a live vector
-            JVec<T, V>::load(z1 + c, d1[k]);
-            JVec<T, V>::load(z2 + c, d2[k]);
+            VecIO<T, V>::load(z1 + c, d1[k]);
+            VecIO<T, V>::load(z2 + c, d2[k]);
         }
     }
 
@@ -215,24 +154,17 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_rows_kernel(
         const bool y_ok = y64 >= 0 && y64 < C;
         bad = bad || (valid && !y_ok);
         const int y = y_ok ? (int)y64 : 0;
-        float zy[2];
-        {
-            float t[1];
-            JVec<T, 1>::load(z1 + rr * ld1 + y, t);
-            zy[0] = t[0];
-            JVec<T, 1>::load(z2 + rr * ld2 + y, t);
-            zy[1] = t[0];
-        }
+        const float zy1 = load1(z1 + rr * ld1, y), zy2 = load1(z2 + rr * ld2, y);
         r.stats(g, y);
         if (g == 0 && valid) {
             // CE = log sum exp(z - max) - (z_y - max), as torch evaluates it; a label out of range gives NaN
             const float nan = __builtin_nanf("");
-            const float ce1 = y_ok ? r.ls1 - (zy[0] - r.m1_) : nan;
-            const float ce2 = y_ok ? r.ls2 - (zy[1] - r.m2_) : nan;
+            const float ce1 = y_ok ? r.ls1 - (zy1 - r.m1_) : nan;
+            const float ce2 = y_ok ? r.ls2 - (zy2 - r.m2_) : nan;
             loss_pick[row] = jc_pick_ce(ce1, ce2, c1);
             kqp += (double)r.kl_qp;
             kpq += (double)r.kl_pq;
-            hits += (y_ok && zy[0] == r.m1_ && r.earlier == 0) ? 1.0 : 0.0;
+            hits += (y_ok && zy1 == r.m1_ && r.earlier == 0) ? 1.0 : 0.0;
         }
     }
     if (bad) atomicOr(status, RLVI_ST_RANGE);
@@ -249,7 +181,7 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_grad_kernel(
     constexpr int R = WAVE / G;
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int g = lane & (G - 1), sub = lane / G;
-    const float gain = jc_gain(grad_out, grad_scale);
+    const float gain = grad_gain(grad_out != nullptr ? *grad_out : 1.0f, grad_scale);
     // d L / d loss_pick_i = g / k on the selected rows; the KL scalars collect it from all k of them: g lambda / B.
     // k = 0: torch.mean of nothing is NaN and nothing flows back -- both gradients are zero.
     const float c_ce = k > 0 ? (gain / (float)k) * c1 : 0.0f;
@@ -282,8 +214,8 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_grad_kernel(
                 o1[j] = cs * (p - hot) + c_kl * ((p - q) + p * (diff - r.kl_pq));
                 o2[j] = cs * (q - hot) + c_kl * ((q - p) + q * (-diff - r.kl_qp));
             }
-            if (g1 != nullptr) JVec<T, V>::store(g1 + rr * ldg1 + col, o1);
-            if (g2 != nullptr) JVec<T, V>::store(g2 + rr * ldg2 + col, o2);
+            if (g1 != nullptr) VecIO<T, V>::store(g1 + rr * ldg1 + col, o1);
+            if (g2 != nullptr) VecIO<T, V>::store(g2 + rr * ldg2 + col, o2);
         }
     }
 }
@@ -295,21 +227,14 @@ struct LongStats {
 };
 
 template <typename T>
-__device__ __forceinline__ float jc_at(const T *p, int c) {
-    float t[1];
-    JVec<T, 1>::load(p + c, t);
-    return t[0];
-}
-
-template <typename T>
 __device__ __forceinline__ LongStats long_stats(const T *z1, const T *z2, int C, int lane, int y) {
     LongStats st;
     float m1 = -__builtin_inff(), m2 = -__builtin_inff();
-    for (int c = lane; c < C; c += WAVE) { m1 = fmaxf(m1, jc_at(z1, c)); m2 = fmaxf(m2, jc_at(z2, c)); }
+    for (int c = lane; c < C; c += WAVE) { m1 = fmaxf(m1, load1(z1, c)); m2 = fmaxf(m2, load1(z2, c)); }
     m1 = wave_max(m1);
     m2 = wave_max(m2);
     float a1 = 0.0f, a2 = 0.0f;
-    for (int c = lane; c < C; c += WAVE) { a1 += mexp(jc_at(z1, c) - m1); a2 += mexp(jc_at(z2, c) - m2); }
+    for (int c = lane; c < C; c += WAVE) { a1 += mexp(load1(z1, c) - m1); a2 += mexp(load1(z2, c) - m2); }
     st.s1 = wave_sum(a1);
     st.s2 = wave_sum(a2);
     st.ls1 = logf(st.s1);
@@ -318,7 +243,7 @@ __device__ __forceinline__ LongStats long_stats(const T *z1, const T *z2, int C,
     float kpq = 0.0f, kqp = 0.0f;
     int ea = 0;
     for (int c = lane; c < C; c += WAVE) {
-        const float e1 = jc_at(z1, c) - m1, e2 = jc_at(z2, c) - m2;
+        const float e1 = load1(z1, c) - m1, e2 = load1(z2, c) - m2;
         const float diff = (e1 - st.ls1) - (e2 - st.ls2);
         kpq += (mexp(e1) * r1) * diff;
         kqp -= (mexp(e2) * r2) * diff;
@@ -348,7 +273,7 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_rows_long_kernel(
         const T *r1 = z1 + row * ld1, *r2 = z2 + row * ld2;
         const LongStats st = long_stats(r1, r2, C, lane, y);
         if (lane == 0) {
-            const float zy1 = jc_at(r1, y), zy2 = jc_at(r2, y);
+            const float zy1 = load1(r1, y), zy2 = load1(r2, y);
             const float nan = __builtin_nanf("");
             const float ce1 = y_ok ? st.ls1 - (zy1 - st.m1) : nan;
             const float ce2 = y_ok ? st.ls2 - (zy2 - st.m2) : nan;
@@ -369,7 +294,7 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_grad_long_kernel(
     const float *__restrict__ grad_out, const float *__restrict__ grad_scale, T *__restrict__ g1, int64_t ldg1,
     T *__restrict__ g2, int64_t ldg2) {
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const float gain = jc_gain(grad_out, grad_scale);
+    const float gain = grad_gain(grad_out != nullptr ? *grad_out : 1.0f, grad_scale);
     const float c_ce = k > 0 ? (gain / (float)k) * c1 : 0.0f;
     const float c_kl = k > 0 ? gain * lam / (float)B : 0.0f;
     for (int64_t row = (int64_t)blockIdx.x * JC_WAVES + wave; row < B; row += (int64_t)gridDim.x * JC_WAVES) {
@@ -381,18 +306,18 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_grad_long_kernel(
         const float cs = (sel[row] != 0.0f && y_ok) ? c_ce : 0.0f;
         const float i1 = 1.0f / st.s1, i2 = 1.0f / st.s2;
         for (int c = lane; c < C; c += WAVE) {
-            const float e1 = jc_at(r1, c) - st.m1, e2 = jc_at(r2, c) - st.m2;
+            const float e1 = load1(r1, c) - st.m1, e2 = load1(r2, c) - st.m2;
             const float p = mexp(e1) * i1, q = mexp(e2) * i2;
             const float diff = (e1 - st.ls1) - (e2 - st.ls2);
             const float hot = c == y ? 1.0f : 0.0f;
             float o[1];
             if (g1 != nullptr) {
                 o[0] = cs * (p - hot) + c_kl * ((p - q) + p * (diff - st.kl_pq));
-                JVec<T, 1>::store(g1 + row * ldg1 + c, o);
+                VecIO<T, 1>::store(g1 + row * ldg1 + c, o);
             }
             if (g2 != nullptr) {
                 o[0] = cs * (q - hot) + c_kl * ((q - p) + q * (-diff - st.kl_qp));
-                JVec<T, 1>::store(g2 + row * ldg2 + c, o);
+                VecIO<T, 1>::store(g2 + row * ldg2 + c, o);
             }
         }
     }
@@ -400,24 +325,20 @@ __global__ __launch_bounds__(JC_THREADS) void jocor_grad_long_kernel(
 
 // ---- selection: one workgroup -----------------------------------------------------------------------------
 // The records of pass 1 in a fixed order -> K_qp, K_pq (rounded to fp32, as the reference's 0-dim tensors are);
-// loss_pick_i = (a_i + lambda K_qp) + lambda K_pq in fp32; the k smallest by the radix select of select.hip
-// (select_smallest_kernel: four 8-bit passes on the order-preserving key, equal values in index order, NaN last);
-// L = their mean (fp64 sum in a fixed order).  Reads a_i from loss_pick and writes loss_pick_i back over it (each
-// thread only its own rows, after its last read of them).  Clears the records it consumed.
-__global__ __launch_bounds__(JC_SEL_BLOCK) void jocor_select_kernel(float *__restrict__ loss_pick, int64_t n,
-                                                                    int64_t k, float lam, double *__restrict__ part,
-                                                                    int nrec, float *__restrict__ sel,
-                                                                    float *__restrict__ out) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned sh_prefix, sh_need, sh_ties;
-    __shared__ unsigned wcount[JC_SEL_NW];
-    __shared__ double shd[3 * JC_SEL_NW];
+// loss_pick_i = (a_i + lambda K_qp) + lambda K_pq in fp32; the k smallest by select_smallest_block (rlvi_select.h:
+// equal values in index order, NaN last); L = their mean (fp64 sum in a fixed order).  Reads a_i from loss_pick and
+// writes loss_pick_i back over it.  Clears the records it consumed.
+__global__ __launch_bounds__(SEL_BLOCK) void jocor_select_kernel(float *__restrict__ loss_pick, int64_t n,
+                                                                 int64_t k, float lam, double *__restrict__ part,
+                                                                 int nrec, float *__restrict__ sel,
+                                                                 float *__restrict__ out) {
+    __shared__ double shd[3 * SEL_NW];
     __shared__ float sh_k[2];
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1), wave = tid / WAVE;
 
     double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-    for (int i = tid; i < nrec; i += JC_SEL_BLOCK) {
+    for (int i = tid; i < nrec; i += SEL_BLOCK) {
         r0 += part[(size_t)PART_STRIDE * i];
         r1 += part[(size_t)PART_STRIDE * i + 1];
         r2 += part[(size_t)PART_STRIDE * i + 2];
@@ -427,154 +348,38 @@ __global__ __launch_bounds__(JC_SEL_BLOCK) void jocor_select_kernel(float *__res
     r2 = wave_sum(r2);
     if (lane == 0) { shd[3 * wave] = r0; shd[3 * wave + 1] = r1; shd[3 * wave + 2] = r2; }
     __syncthreads();
-    for (int i = tid; i < nrec; i += JC_SEL_BLOCK)
+    for (int i = tid; i < nrec; i += SEL_BLOCK)
 #pragma unroll
         for (int c = 0; c < PART_STRIDE; ++c) part[(size_t)PART_STRIDE * i + c] = 0.0;
     if (tid == 0) {
         double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-        for (int w = 0; w < JC_SEL_NW; ++w) { t0 += shd[3 * w]; t1 += shd[3 * w + 1]; t2 += shd[3 * w + 2]; }
+        for (int w = 0; w < SEL_NW; ++w) { t0 += shd[3 * w]; t1 += shd[3 * w + 1]; t2 += shd[3 * w + 2]; }
         const float kqp = (float)(t0 / (double)n), kpq = (float)(t1 / (double)n);
         sh_k[0] = __fmul_rn(lam, kqp);
         sh_k[1] = __fmul_rn(lam, kpq);
         out[1] = kqp;
         out[2] = kpq;
         out[3] = (float)(t2 * 100.0 / (double)n);
-        sh_prefix = 0u;
-        sh_need = (unsigned)(k < 0 ? 0 : k);
     }
     __syncthreads();
     const float lk1 = sh_k[0], lk2 = sh_k[1];
-    auto pick = [&](int64_t i) { return __fadd_rn(__fadd_rn(loss_pick[i], lk1), lk2); };
 
-    const bool none = k <= 0, all = k >= n;
-    unsigned T = 0xFFFFFFFFu, need = 0u, ties = 0u;
-    if (!none && !all) {
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (tid < 256) hist[tid] = 0u;
-            __syncthreads();
-            const unsigned prefix = sh_prefix;
-            // JC_SEL_U independent loads in flight per thread and trip: a trip is latency-bound otherwise
-            for (int64_t base = 0; base < n; base += (int64_t)JC_SEL_U * JC_SEL_BLOCK) {
-                float v[JC_SEL_U];
-#pragma unroll
-                for (int j = 0; j < JC_SEL_U; ++j) {
-                    const int64_t i = base + (int64_t)j * JC_SEL_BLOCK + tid;
-                    v[j] = i < n ? loss_pick[i] : 0.0f;
-                }
-#pragma unroll
-                for (int j = 0; j < JC_SEL_U; ++j) {
-                    const int64_t i = base + (int64_t)j * JC_SEL_BLOCK + tid;
-                    const unsigned key = f32_key(__fadd_rn(__fadd_rn(v[j], lk1), lk2));
-                    const bool cand = i < n && (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8)));
-                    const unsigned bin = (key >> shift) & 255u;
-                    // losses cluster in a few bins of the leading bytes, where 64 lanes adding to one LDS address
-                    // would serialise: one add per bin for the wave's (up to) two most common bins, plain adds
-                    // for the rest
-                    unsigned long long pending = __ballot(cand);
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) {
-                        if (!pending) break;
-                        const int leader = __ffsll((long long)pending) - 1;
-                        const unsigned lb = (unsigned)__shfl((int)bin, leader);
-                        const unsigned long long same = __ballot(cand && bin == lb) & pending;
-                        if (lane == leader) atomicAdd(&hist[lb], (unsigned)__popcll(same));
-                        pending &= ~same;
-                    }
-                    if ((pending >> lane) & 1ull) atomicAdd(&hist[bin], 1u);
-                }
-            }
-            __syncthreads();
-            if (wave == 0) {
-                // the bin holding the need-th candidate: a prefix sum over the 256 bins, four per lane
-                unsigned h[4], tot = 0u;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { h[j] = hist[4 * lane + j]; tot += h[j]; }
-                unsigned inc = tot;
-#pragma unroll
-                for (int o = 1; o < WAVE; o <<= 1) {
-                    const unsigned t = (unsigned)__shfl_up((int)inc, o);
-                    if (lane >= o) inc += t;
-                }
-                const unsigned nd = sh_need;
-                unsigned pre = inc - tot;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (pre < nd && nd <= pre + h[j]) {      // exactly one bin of the wave holds it
-                        sh_need = nd - pre;
-                        sh_prefix = prefix | ((unsigned)(4 * lane + j) << shift);
-                        sh_ties = h[j];
-                    }
-                    pre += h[j];
-                }
-            }
-            __syncthreads();
-        }
-        T = sh_prefix;
-        need = sh_need;
-        ties = sh_ties;
-    }
-    // selection, loss_pick and the fixed-order sum of the kept values
-    double acc = 0.0;
-    unsigned running = 0u;
-    if (none || all || ties == need) {
-        // no ranking among equal values: a key test per row, JC_SEL_U rows in flight per thread
-        for (int64_t base = 0; base < n; base += (int64_t)JC_SEL_U * JC_SEL_BLOCK) {
-            float v[JC_SEL_U];
-#pragma unroll
-            for (int j = 0; j < JC_SEL_U; ++j) {
-                const int64_t i = base + (int64_t)j * JC_SEL_BLOCK + tid;
-                v[j] = i < n ? loss_pick[i] : 0.0f;
-            }
-#pragma unroll
-            for (int j = 0; j < JC_SEL_U; ++j) {
-                const int64_t i = base + (int64_t)j * JC_SEL_BLOCK + tid;
-                if (i < n) {
-                    const float x = __fadd_rn(__fadd_rn(v[j], lk1), lk2);
-                    const bool keep = all || (!none && f32_key(x) <= T);
-                    loss_pick[i] = x;
-                    sel[i] = keep ? 1.0f : 0.0f;
-                    if (keep) acc += (double)x;
-                }
-            }
-        }
-    }
-    for (int64_t base = 0; base < n && !(none || all || ties == need); base += JC_SEL_BLOCK) {
-        const int64_t i = base + tid;
-        const float v = i < n ? pick(i) : 0.0f;
-        const unsigned key = i < n ? f32_key(v) : 0xFFFFFFFFu;
-        bool keep;
-        {
-            const bool tie = i < n && key == T;
-            const unsigned long long bal = __ballot(tie);
-            const unsigned before = (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wcount[wave] = (unsigned)__popcll(bal);
-            __syncthreads();
-            unsigned off = running, total = 0u;
-#pragma unroll
-            for (int w = 0; w < JC_SEL_NW; ++w) {
-                const unsigned c = wcount[w];
-                if (w < wave) off += c;
-                total += c;
-            }
-            keep = key < T || (tie && off + before < need);
-            running += total;
-            __syncthreads();
-        }
-        if (i < n) {
+    double acc = 0.0;                            // the kept values of this thread's rows
+    select_smallest_block(
+        loss_pick, n, k, [&](float a) { return __fadd_rn(__fadd_rn(a, lk1), lk2); },
+        [&](int64_t i, float v, bool keep) {
             loss_pick[i] = v;
             sel[i] = keep ? 1.0f : 0.0f;
             if (keep) acc += (double)v;
-        }
-    }
+        });
     acc = wave_sum(acc);
     __syncthreads();
     if (lane == 0) shd[wave] = acc;
     __syncthreads();
     if (tid == 0) {
         double t = 0.0;
-        for (int w = 0; w < JC_SEL_NW; ++w) t += shd[w];
-        out[0] = none ? __builtin_nanf("") : (float)(t / (double)(all ? n : k));
+        for (int w = 0; w < SEL_NW; ++w) t += shd[w];
+        out[0] = k <= 0 ? __builtin_nanf("") : (float)(t / (double)(k >= n ? n : k));
     }
 }
 
@@ -587,13 +392,7 @@ template <typename T>
 static JcShape jc_pick_shape(const void *z1, int64_t ld1, const void *z2, int64_t ld2, const void *g1, int64_t ldg1,
                              const void *g2, int64_t ldg2, int64_t C) {
     constexpr int VMAX = 16 / (int)sizeof(T);
-    auto ok = [&](int v) {
-        const size_t bytes = (size_t)v * sizeof(T);
-        if (C % v || ld1 % v || ld2 % v || ((uintptr_t)z1 % bytes) || ((uintptr_t)z2 % bytes)) return false;
-        if (g1 && (ldg1 % v || ((uintptr_t)g1 % bytes))) return false;
-        if (g2 && (ldg2 % v || ((uintptr_t)g2 % bytes))) return false;
-        return true;
-    };
+    auto ok = [&](int v) { return vec_fits<T>(v, C, {{z1, ld1}, {z2, ld2}, {g1, ldg1}, {g2, ldg2}}); };
     const int V = ok(VMAX) ? VMAX : ok(2) ? 2 : 1;
     const int64_t nv = C / V;
     for (int G : {4, 16, 64})
@@ -655,7 +454,7 @@ static int jocor_fwd(const T *z1, int64_t ld1, const T *z2, int64_t ld2, const i
 #undef RLVI_JR
     }
     if (rc) return rc;
-    return launch(jocor_select_kernel, dim3(1), dim3(JC_SEL_BLOCK), 0, st, loss_pick, B, k, lam, part, (int)nb, sel,
+    return launch(jocor_select_kernel, dim3(1), dim3(SEL_BLOCK), 0, st, loss_pick, B, k, lam, part, (int)nb, sel,
                   out);
 }
 

@@ -19,130 +19,10 @@
 
 namespace rlvi {
 
-#ifndef RLVI_MSTEP_NT
-#define RLVI_MSTEP_NT 0   // bit 0: nontemporal row loads, bit 1: nontemporal gradient stores
-#endif
-typedef float vf4 __attribute__((ext_vector_type(4)));
-typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef unsigned int vu4 __attribute__((ext_vector_type(4)));
-typedef unsigned int vu2 __attribute__((ext_vector_type(2)));
-
-template <typename T, int V>
-struct VecIO;
-
-// default streaming forms = the plain forms (specialisations below override where it pays)
-template <typename T, int V, class Self>
-struct VecIOBase {
-    static __device__ __forceinline__ void load_stream(const T *p, float (&v)[V]) { Self::load(p, v); }
-    static __device__ __forceinline__ void store_stream(T *p, const float (&v)[V]) { Self::store(p, v); }
-};
-
-template <>
-struct VecIO<float, 4> {
-    static __device__ __forceinline__ void load(const float *p, float (&v)[4]) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[4]) {
-        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    // streaming forms: read-once / write-once data bypasses cache retention (`nt`)
-    static __device__ __forceinline__ void load_stream(const float *p, float (&v)[4]) {
-#if RLVI_MSTEP_NT & 1
-        const vf4 t = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(p));
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-#else
-        load(p, v);
-#endif
-    }
-    static __device__ __forceinline__ void store_stream(float *p, const float (&v)[4]) {
-#if RLVI_MSTEP_NT & 2
-        const vf4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<vf4 *>(p));
-#else
-        store(p, v);
-#endif
-    }
-};
-template <>
-struct VecIO<float, 2> : VecIOBase<float, 2, VecIO<float, 2>> {
-    static __device__ __forceinline__ void load(const float *p, float (&v)[2]) {
-        const float2 t = *reinterpret_cast<const float2 *>(p);
-        v[0] = t.x; v[1] = t.y;
-    }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[2]) {
-        *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-    }
-};
-template <>
-struct VecIO<float, 1> : VecIOBase<float, 1, VecIO<float, 1>> {
-    static __device__ __forceinline__ void load(const float *p, float (&v)[1]) { v[0] = *p; }
-    static __device__ __forceinline__ void store(float *p, const float (&v)[1]) { *p = v[0]; }
-};
-// 2-byte elements (T = uint16_t: bf16, T = f16_t: fp16): widened to fp32 and narrowed back through Half<T>
-template <typename T>
-struct VecIO<T, 8> : VecIOBase<T, 8, VecIO<T, 8>> {
-    static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
-        const uint4 t = *reinterpret_cast<const uint4 *>(p);
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = Half<T>::lo(w[i]);
-            v[2 * i + 1] = Half<T>::hi(w[i]);
-        }
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[8]) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = Half<T>::narrow2(v[2 * i], v[2 * i + 1]);
-        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-};
-template <typename T>
-struct VecIO<T, 4> : VecIOBase<T, 4, VecIO<T, 4>> {
-    static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
-        const uint2 t = *reinterpret_cast<const uint2 *>(p);
-        v[0] = Half<T>::lo(t.x); v[1] = Half<T>::hi(t.x);
-        v[2] = Half<T>::lo(t.y); v[3] = Half<T>::hi(t.y);
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[4]) {
-        uint2 t;
-        t.x = Half<T>::narrow2(v[0], v[1]);
-        t.y = Half<T>::narrow2(v[2], v[3]);
-        *reinterpret_cast<uint2 *>(p) = t;
-    }
-};
-template <typename T>
-struct VecIO<T, 2> : VecIOBase<T, 2, VecIO<T, 2>> {
-    static __device__ __forceinline__ void load(const T *p, float (&v)[2]) {
-        const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
-        v[0] = Half<T>::lo(t); v[1] = Half<T>::hi(t);
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[2]) {
-        *reinterpret_cast<uint32_t *>(p) = Half<T>::narrow2(v[0], v[1]);
-    }
-};
-template <typename T>
-struct VecIO<T, 1> : VecIOBase<T, 1, VecIO<T, 1>> {
-    static __device__ __forceinline__ void load(const T *p, float (&v)[1]) {
-        v[0] = Half<T>::widen(*reinterpret_cast<const uint16_t *>(p));
-    }
-    static __device__ __forceinline__ void store(T *p, const float (&v)[1]) {
-        *reinterpret_cast<uint16_t *>(p) = Half<T>::narrow(v[0]);
-    }
-};
 
 constexpr int MSTEP_THREADS = 256;
 constexpr int MSTEP_WAVES = MSTEP_THREADS / WAVE;
-
-// The gradient's factor: inv_scale times the loss scale that a GradScaler keeps on the device (grad_scale, fp16
-// entries; NULL: none).  Read by the kernel, so a training loop needs no host sync per batch.  The loss, the records
-// and the residuals never see the scale.  (Wave-uniform: readfirstlane keeps it in an SGPR, as inv_scale is.)
-__device__ __forceinline__ float grad_gain(float inv_scale, const float *grad_scale) {
-    const float g = grad_scale != nullptr ? inv_scale * *grad_scale : inv_scale;
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g)));
-}
 
 // Per-block partial record.  accum == 0: overwrite (a finalize launch follows); accum == 1: add
 // to what earlier mini-batches of this epoch left there (rlvi_epoch_end_f32 reduces and clears).
@@ -185,7 +65,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
     const int g = lane & (G - 1);
     const int sub = lane / G;
     const float NEG_INF = -__builtin_inff();
-    const float gscale = grad_gain(inv_scale, grad_scale);
+    const float gscale = grad_gain(inv_scale, grad_scale);   // the loss, records and residuals never see grad_scale
 
     float acc = 0.0f;   // sum of pi*l over the rows whose lane-group leader this lane is
     float hits = 0.0f;
@@ -1271,12 +1151,7 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
         return RLVI_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // widest vector for which every row start and the row length are aligned
-    auto ok = [&](int v) {
-        const size_t bytes = (size_t)v * sizeof(T);
-        if (C % v || ld % v || ((uintptr_t)logits % bytes)) return false;
-        if (grad && (ldg % v || ((uintptr_t)grad % bytes))) return false;
-        return true;
-    };
+    auto ok = [&](int v) { return vec_fits<T>(v, C, {{logits, ld}, {grad, ldg}}); };
     constexpr int VMAX = 16 / (int)sizeof(T);
     const int Ci = (int)C;
     if constexpr (sizeof(T) == 2) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <tuple>
 #include <utility>
 
@@ -371,5 +372,147 @@ struct Half<f16_t> {                                              // fp16
         return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
     }
 };
+
+#ifndef RLVI_MSTEP_NT
+#define RLVI_MSTEP_NT 0   // the *_stream forms (the M-step's): bit 0 nontemporal loads, bit 1 nontemporal stores
+#endif
+typedef float vf4 __attribute__((ext_vector_type(4)));
+
+// V consecutive elements of T <-> fp32: fp32 vectors of 1, 2 or 4, 2-byte vectors (bf16, fp16) of 1, 2, 4 or 8
+// elements, widened and narrowed through Half<T>.  V elements must be V * sizeof(T)-byte aligned (vec_fits).
+template <typename T, int V>
+struct VecIO;
+
+// default streaming forms = the plain forms (specialisations below override where it pays)
+template <typename T, int V, class Self>
+struct VecIOBase {
+    static __device__ __forceinline__ void load_stream(const T *p, float (&v)[V]) { Self::load(p, v); }
+    static __device__ __forceinline__ void store_stream(T *p, const float (&v)[V]) { Self::store(p, v); }
+};
+
+template <>
+struct VecIO<float, 4> {
+    static __device__ __forceinline__ void load(const float *p, float (&v)[4]) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+    static __device__ __forceinline__ void store(float *p, const float (&v)[4]) {
+        *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    // streaming forms: read-once / write-once data bypasses cache retention (`nt`)
+    static __device__ __forceinline__ void load_stream(const float *p, float (&v)[4]) {
+#if RLVI_MSTEP_NT & 1
+        const vf4 t = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(p));
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+#else
+        load(p, v);
+#endif
+    }
+    static __device__ __forceinline__ void store_stream(float *p, const float (&v)[4]) {
+#if RLVI_MSTEP_NT & 2
+        const vf4 t = {v[0], v[1], v[2], v[3]};
+        __builtin_nontemporal_store(t, reinterpret_cast<vf4 *>(p));
+#else
+        store(p, v);
+#endif
+    }
+};
+template <>
+struct VecIO<float, 2> : VecIOBase<float, 2, VecIO<float, 2>> {
+    static __device__ __forceinline__ void load(const float *p, float (&v)[2]) {
+        const float2 t = *reinterpret_cast<const float2 *>(p);
+        v[0] = t.x; v[1] = t.y;
+    }
+    static __device__ __forceinline__ void store(float *p, const float (&v)[2]) {
+        *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
+    }
+};
+template <>
+struct VecIO<float, 1> : VecIOBase<float, 1, VecIO<float, 1>> {
+    static __device__ __forceinline__ void load(const float *p, float (&v)[1]) { v[0] = *p; }
+    static __device__ __forceinline__ void store(float *p, const float (&v)[1]) { *p = v[0]; }
+};
+// 2-byte elements (T = uint16_t: bf16, T = f16_t: fp16): widened to fp32 and narrowed back through Half<T>
+template <typename T>
+struct VecIO<T, 8> : VecIOBase<T, 8, VecIO<T, 8>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
+        const uint4 t = *reinterpret_cast<const uint4 *>(p);
+        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = Half<T>::lo(w[i]);
+            v[2 * i + 1] = Half<T>::hi(w[i]);
+        }
+    }
+    static __device__ __forceinline__ void store(T *p, const float (&v)[8]) {
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            w[i] = Half<T>::narrow2(v[2 * i], v[2 * i + 1]);
+        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+template <typename T>
+struct VecIO<T, 4> : VecIOBase<T, 4, VecIO<T, 4>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
+        const uint2 t = *reinterpret_cast<const uint2 *>(p);
+        v[0] = Half<T>::lo(t.x); v[1] = Half<T>::hi(t.x);
+        v[2] = Half<T>::lo(t.y); v[3] = Half<T>::hi(t.y);
+    }
+    static __device__ __forceinline__ void store(T *p, const float (&v)[4]) {
+        uint2 t;
+        t.x = Half<T>::narrow2(v[0], v[1]);
+        t.y = Half<T>::narrow2(v[2], v[3]);
+        *reinterpret_cast<uint2 *>(p) = t;
+    }
+};
+template <typename T>
+struct VecIO<T, 2> : VecIOBase<T, 2, VecIO<T, 2>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[2]) {
+        const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
+        v[0] = Half<T>::lo(t); v[1] = Half<T>::hi(t);
+    }
+    static __device__ __forceinline__ void store(T *p, const float (&v)[2]) {
+        *reinterpret_cast<uint32_t *>(p) = Half<T>::narrow2(v[0], v[1]);
+    }
+};
+template <typename T>
+struct VecIO<T, 1> : VecIOBase<T, 1, VecIO<T, 1>> {
+    static __device__ __forceinline__ void load(const T *p, float (&v)[1]) {
+        v[0] = Half<T>::widen(*reinterpret_cast<const uint16_t *>(p));
+    }
+    static __device__ __forceinline__ void store(T *p, const float (&v)[1]) {
+        *reinterpret_cast<uint16_t *>(p) = Half<T>::narrow(v[0]);
+    }
+};
+
+// element i of p as fp32
+template <typename T>
+__device__ __forceinline__ float load1(const T *p, int i) {
+    float v[1];
+    VecIO<T, 1>::load(p + i, v);
+    return v[0];
+}
+
+// A gradient's factor g times the loss scale that a GradScaler keeps on the device (NULL: none), read by the kernel
+// so that a training loop needs no host sync per batch.  Wave-uniform: readfirstlane keeps it in an SGPR.
+__device__ __forceinline__ float grad_gain(float g, const float *scale) {
+    const float s = scale != nullptr ? g * *scale : g;
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s)));
+}
+
+// Host: whether vectors of v elements of T fit a row of C elements and every block of rows: its row pitch (in
+// elements) a multiple of v and its base pointer v * sizeof(T)-byte aligned.  Blocks with a null pointer are skipped.
+struct RowBlock {
+    const void *p;
+    int64_t ld;
+};
+template <typename T>
+inline bool vec_fits(int v, int64_t C, std::initializer_list<RowBlock> blocks) {
+    if (C % v) return false;
+    for (const RowBlock &b : blocks)
+        if (b.p && (b.ld % v || (uintptr_t)b.p % ((size_t)v * sizeof(T)))) return false;
+    return true;
+}
 
 }  // namespace rlvi

@@ -19,10 +19,6 @@ constexpr int TOPK_MAXK = 8;              // k values per call
 
 struct TopkList { int k[TOPK_MAXK]; };
 
-__device__ __forceinline__ float topk_widen(float v) { return v; }
-__device__ __forceinline__ float topk_widen(uint16_t v) { return Half<uint16_t>::widen(v); }      // bf16
-__device__ __forceinline__ float topk_widen(f16_t v) { return (float)v; }                             // fp16 (exact)
-
 // G = lanes per row (a power of two, chosen by the launcher so that a lane holds at most eight elements of rows up
 // to 512 columns): 64 / G rows per wave at once, their elements asked for BEFORE the label's logit is known (the
 // label -> logit chain is two dependent round trips), longer rows streamed behind it.
@@ -49,7 +45,7 @@ __global__ __launch_bounds__(TOPK_THREADS, 1) void topk_hits_kernel(const T *__r
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = g + j * G;
-                v[j] = topk_widen(z[c < C ? c : g < C ? g : 0]);
+                v[j] = load1(z, c < C ? c : g < C ? g : 0);
             }
         }
         const bool ok = valid && y64 >= 0 && y64 < C;   // a label outside [0, C) matches no prediction (utils.py:72)
@@ -69,9 +65,9 @@ __global__ __launch_bounds__(TOPK_THREADS, 1) void topk_hits_kernel(const T *__r
                 ahead += (c < C && (v[j] > zy || (v[j] == zy && c < y))) ? 1 : 0;
             }
         } else {
-            zy = topk_widen(z[y]);
+            zy = load1(z, y);
             for (int c = g; c < C; c += G) {
-                const float x = topk_widen(z[c]);
+                const float x = load1(z, c);
                 ahead += (x > zy || (x == zy && c < y)) ? 1 : 0;
             }
         }

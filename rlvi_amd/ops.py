@@ -117,17 +117,41 @@ def workspace(device, n=0, b=0):
     return ws
 
 
-_NATIVE = (torch.float32, torch.bfloat16, torch.float16)      # logit dtypes with entries of their own
+# logit dtypes with C entries of their own, and the entries' name suffixes
+_SUFFIX = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+_NATIVE = tuple(_SUFFIX)
 
 
-def _check_grad_scale(grad_scale, device):
-    """A loss scale (torch.amp.GradScaler's scale tensor): one fp32 value on the logits' device, read there."""
-    if grad_scale is None:
-        return None
-    if not torch.is_tensor(grad_scale) or grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 \
-            or grad_scale.device != device:
-        raise ValueError("grad_scale must be a one-element fp32 tensor on the logits' device")
-    return grad_scale
+def _entry(L, stem, dtype):
+    """The C entry rlvi_<stem>_<f32 | bf16 | f16> for logits of a native dtype."""
+    return getattr(L, f"rlvi_{stem}_{_SUFFIX[dtype]}")
+
+
+def _as_logits(logits):
+    """Logits as the C entries take them: a native dtype (any other goes to fp32), unit column stride."""
+    if logits.dtype not in _NATIVE:
+        logits = logits.float()
+    return logits if logits.stride(1) == 1 else logits.contiguous()
+
+
+def _as_int64(t):
+    """Labels or sample indexes as a contiguous int64 vector."""
+    return t if t.dtype == torch.int64 and t.is_contiguous() else t.to(torch.int64).contiguous()
+
+
+def _check_f32_vectors(what, *tensors):
+    """Vectors that a kernel reads or writes in place: each must be a contiguous 1-D fp32 tensor."""
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"{what} must be contiguous 1-D fp32 tensors")
+
+
+def _check_grad_scale(t, device, what="grad_scale"):
+    """A one-element fp32 tensor on the logits' device that the kernel reads there (a GradScaler's scale, an upstream
+    gradient), or None."""
+    if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != 1 or t.device != device):
+        raise ValueError(f"{what} must be a one-element fp32 tensor on the logits' device")
+    return t
 
 
 def _mstep_call(L, logits, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad, out, ws):
@@ -136,13 +160,12 @@ def _mstep_call(L, logits, labels, idx, weights, residuals, N, B, C, inv_scale, 
     args = (_ptr(logits), logits.stride(0), _ptr(labels), _ptr(idx), _ptr(weights), _ptr(residuals), N, B, C,
             float(inv_scale))
     tail = (_ptr(grad), grad.stride(0) if grad is not None else 0, _ptr(out), ws.ptr, _stream_ptr())
+    fn = _entry(L, "mstep_fwd_bwd", logits.dtype)
     if logits.dtype == torch.float16:
-        rc = L.rlvi_mstep_fwd_bwd_f16(*args, _ptr(grad_scale), *tail)
-    else:
-        fn = L.rlvi_mstep_fwd_bwd_f32 if logits.dtype == torch.float32 else L.rlvi_mstep_fwd_bwd_bf16
-        rc = fn(*args, *tail)
-        if rc == 0 and grad is not None and grad_scale is not None:
-            grad.mul_(grad_scale)
+        return fn(*args, _ptr(grad_scale), *tail)
+    rc = fn(*args, *tail)
+    if rc == 0 and grad is not None and grad_scale is not None:
+        grad.mul_(grad_scale)
     return rc
 
 
@@ -164,14 +187,9 @@ def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_
     if logits.dim() != 2:
         raise ValueError("logits must be [B, C]")
     B, C = logits.shape
-    if logits.dtype not in _NATIVE:
-        logits = logits.float()
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    if labels.dtype != torch.int64 or not labels.is_contiguous():
-        labels = labels.to(torch.int64).contiguous()
-    if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous()):
-        idx = idx.to(torch.int64).contiguous()
+    logits, labels = _as_logits(logits), _as_int64(labels)
+    if idx is not None:
+        idx = _as_int64(idx)
     if weights.dtype != torch.float32 or not weights.is_contiguous():
         raise ValueError("weights must be a contiguous fp32 vector (it is read in place)")
     if residuals is not None and (residuals.dtype != torch.float32 or not residuals.is_contiguous()):
@@ -226,9 +244,7 @@ class MStepLoop:
     def __init__(self, weights, residuals, ws=None):
         L = _lib.load()
         _require_gpu(weights, residuals)
-        for t in (weights, residuals):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError("weights / residuals must be contiguous 1-D fp32 tensors")
+        _check_f32_vectors("weights / residuals", weights, residuals)
         if residuals.shape != weights.shape:
             raise ValueError("residuals and weights differ in length")
         self.weights, self.residuals = weights, residuals
@@ -236,7 +252,7 @@ class MStepLoop:
         self.ws = ws or workspace(weights.device, self.N, 0)
         self._w, self._r, self._wsp = weights.data_ptr(), residuals.data_ptr(), self.ws.buf.data_ptr()
         self._stream = torch.cuda.current_stream(weights.device).cuda_stream
-        self._f32, self._bf16, self._f16 = L.rlvi_mstep_fwd_bwd_f32, L.rlvi_mstep_fwd_bwd_bf16, L.rlvi_mstep_fwd_bwd_f16
+        self._f32, self._bf16, self._f16 = (_entry(L, "mstep_fwd_bwd", dt) for dt in _NATIVE)   # bound once
         self._grads = {}
         self._dev = weights.device
         self._devidx = weights.device.index if weights.device.index is not None else torch.cuda.current_device()
@@ -283,9 +299,7 @@ def estep_deep(residuals, weights, tol=1e-3, maxiter=40, iters=None, trace=None,
     """update_sample_weights (train_rlvi.py:14-38), in place on both vectors."""
     L = _lib.load()
     _require_gpu(residuals, weights)
-    for t in (residuals, weights):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("residuals / weights must be contiguous 1-D fp32 tensors")
+    _check_f32_vectors("residuals / weights", residuals, weights)
     if residuals.shape != weights.shape:
         raise ValueError("residuals and weights differ in length")
     N = weights.shape[0]
@@ -301,11 +315,7 @@ def evaluate_batch(logits, labels, out=None, ws=None):
     CE, hits}."""
     L = _lib.load()
     _require_gpu(logits, labels)
-    if logits.dtype not in _NATIVE:
-        logits = logits.float()
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    labels = labels.to(torch.int64).contiguous()
+    logits, labels = _as_logits(logits), _as_int64(labels)
     B, C = logits.shape
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=logits.device)
@@ -340,9 +350,7 @@ def estep_sharded(residuals, weights, n_all, tol=1e-3, maxiter=40, iters=None, w
     M-step scalars of the epoch (as epoch_end)."""
     L = _lib.load()
     _require_gpu(residuals, weights)
-    for t in (residuals, weights):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("residuals / weights must be contiguous 1-D fp32 tensors")
+    _check_f32_vectors("residuals / weights", residuals, weights)
     if ws is None:
         raise ValueError("the sharded E-step needs the workspace whose peer table was set up")
     _refuse_stale_peers(ws)
@@ -358,8 +366,7 @@ def threshold_truncate_sharded(weights, n_all, threshold, alpha=0.05, want_mask=
     Returns (threshold, mask of this rank's weights or None, kept over all ranks) -- rank-identical."""
     L = _lib.load()
     _require_gpu(weights)
-    if weights.dtype != torch.float32 or not weights.is_contiguous() or weights.dim() != 1:
-        raise ValueError("weights must be a contiguous 1-D fp32 tensor")
+    _check_f32_vectors("weights", weights)
     if ws is None:
         raise ValueError("the sharded threshold needs the workspace whose peer table was set up")
     _refuse_stale_peers(ws)
@@ -381,9 +388,7 @@ def epoch_end(residuals, weights, overfit=False, threshold=0, batches=0, tol=1e-
     a 0-dim device tensor after truncation ran; out is None when batches == 0."""
     L = _lib.load()
     _require_gpu(residuals, weights)
-    for t in (residuals, weights):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("residuals / weights must be contiguous 1-D fp32 tensors")
+    _check_f32_vectors("residuals / weights", residuals, weights)
     N = weights.shape[0]
     ws = ws or workspace(weights.device, N, 0)
     thr = None
@@ -443,7 +448,7 @@ def fused_em(logits, labels, pi, tol=1e-3, maxiter=40, inv_scale=None, want_grad
         logits = logits.float()
     if logits.stride(1) != 1:
         logits = logits.contiguous()
-    labels = labels.to(torch.int64).contiguous()
+    labels = _as_int64(labels)
     B, C = logits.shape
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=logits.device)
@@ -603,8 +608,7 @@ def select_smallest(losses, k, out=None):
     index order.  One launch, no host round trip."""
     L = _lib.load()
     _require_gpu(losses)
-    if losses.dtype != torch.float32 or not losses.is_contiguous() or losses.dim() != 1:
-        raise ValueError("losses must be a contiguous 1-D fp32 tensor")
+    _check_f32_vectors("losses", losses)
     if out is None:
         out = torch.empty_like(losses)
     _lib.check(L.rlvi_select_smallest_f32(_ptr(losses), losses.shape[0], int(k), _ptr(out),
@@ -616,7 +620,6 @@ def topk_hits(logits, labels, ks, out=None):
     """Rows of the batch whose label is among the k largest logits, for every k of `ks` (at most 8): the counts
     behind accuracy(logit, target, topk) of deep-learning/utils.py:65-79.  Returns a device int32 tensor [len(ks)]
     (no host synchronisation here).  RuntimeError when a k exceeds the number of classes, as torch.topk raises."""
-    import ctypes
     L = _lib.load()
     _require_gpu(logits, labels)
     if logits.dim() != 2:
@@ -627,17 +630,11 @@ def topk_hits(logits, labels, ks, out=None):
         raise ValueError("between one and eight values of k per call")
     if max(ks) > C or min(ks) < 1:
         raise RuntimeError("selected index k out of range")
-    if logits.dtype not in _NATIVE:
-        logits = logits.float()
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    if labels.dtype != torch.int64 or not labels.is_contiguous():
-        labels = labels.to(torch.int64).contiguous()
+    logits, labels = _as_logits(logits), _as_int64(labels)
     if out is None:
         out = torch.empty(len(ks), dtype=torch.int32, device=logits.device)
     karr = (ctypes.c_int32 * len(ks))(*ks)
-    fn = {torch.float32: L.rlvi_topk_hits_f32, torch.bfloat16: L.rlvi_topk_hits_bf16,
-          torch.float16: L.rlvi_topk_hits_f16}[logits.dtype]
+    fn = _entry(L, "topk_hits", logits.dtype)
     _lib.check(fn(_ptr(logits), logits.stride(0), _ptr(labels), B, C, karr, len(ks), _ptr(out), _stream_ptr()),
                "rlvi_topk_hits")
     return out
@@ -677,11 +674,6 @@ def weighted_cross_entropy(logits, labels, idx, weights, residuals, inv_scale=No
     return _WeightedCE.apply(logits, labels, idx, weights, residuals, inv_scale)
 
 
-_JOCOR_ENTRIES = {torch.float32: ("rlvi_jocor_fwd_f32", "rlvi_jocor_bwd_f32"),
-                  torch.bfloat16: ("rlvi_jocor_fwd_bf16", "rlvi_jocor_bwd_bf16"),
-                  torch.float16: ("rlvi_jocor_fwd_f16", "rlvi_jocor_bwd_f16")}
-
-
 def _jocor_blocks(logits1, logits2, labels):
     """Both blocks in one native dtype (their own if they share one, else fp32), unit column stride; int64 labels."""
     _require_gpu(logits1, logits2, labels)
@@ -689,15 +681,9 @@ def _jocor_blocks(logits1, logits2, labels):
         raise ValueError("logits1 and logits2 must both be [B, C]")
     if labels.dim() != 1 or labels.shape[0] != logits1.shape[0]:
         raise ValueError("labels must be a [B] vector")
-    if logits1.dtype != logits2.dtype or logits1.dtype not in _NATIVE:
+    if logits1.dtype != logits2.dtype:
         logits1, logits2 = logits1.float(), logits2.float()
-    if logits1.stride(1) != 1:
-        logits1 = logits1.contiguous()
-    if logits2.stride(1) != 1:
-        logits2 = logits2.contiguous()
-    if labels.dtype != torch.int64 or not labels.is_contiguous():
-        labels = labels.to(torch.int64).contiguous()
-    return logits1, logits2, labels
+    return _as_logits(logits1), _as_logits(logits2), _as_int64(labels)
 
 
 def jocor_forward(logits1, logits2, labels, k, co_lambda=0.1, out=None, ws=None):
@@ -712,7 +698,7 @@ def jocor_forward(logits1, logits2, labels, k, co_lambda=0.1, out=None, ws=None)
     loss_pick = torch.empty(B, dtype=torch.float32, device=dev)
     sel = torch.empty(B, dtype=torch.float32, device=dev)
     ws = ws or workspace(dev)
-    fn = getattr(L, _JOCOR_ENTRIES[logits1.dtype][0])
+    fn = _entry(L, "jocor_fwd", logits1.dtype)
     _lib.check(fn(_ptr(logits1), logits1.stride(0), _ptr(logits2), logits2.stride(0), _ptr(labels), B, C, int(k),
                   float(co_lambda), _ptr(loss_pick), _ptr(sel), _ptr(out), ws.ptr, _stream_ptr()), "rlvi_jocor_fwd")
     return out, loss_pick, sel
@@ -725,12 +711,11 @@ def jocor_backward(logits1, logits2, labels, sel, k, co_lambda=0.1, grad_out=Non
     L = _lib.load()
     B, C = logits1.shape
     dev = logits1.device
-    for t in (grad_out, grad_scale):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != dev):
-            raise ValueError("grad_out / grad_scale must be one-element fp32 tensors on the logits' device")
+    _check_grad_scale(grad_out, dev, "grad_out")
+    _check_grad_scale(grad_scale, dev)
     g1 = torch.empty((B, C), dtype=logits1.dtype, device=dev) if want1 else None
     g2 = torch.empty((B, C), dtype=logits1.dtype, device=dev) if want2 else None
-    fn = getattr(L, _JOCOR_ENTRIES[logits1.dtype][1])
+    fn = _entry(L, "jocor_bwd", logits1.dtype)
     _lib.check(fn(_ptr(logits1), logits1.stride(0), _ptr(logits2), logits2.stride(0), _ptr(labels), _ptr(sel), B, C,
                   int(k), float(co_lambda), _ptr(grad_out), _ptr(grad_scale), _ptr(g1), C if want1 else 0, _ptr(g2),
                   C if want2 else 0, _stream_ptr()), "rlvi_jocor_bwd")
