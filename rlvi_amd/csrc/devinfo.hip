@@ -5,6 +5,7 @@
 //   * coop_blocks(): how many workgroups of a kernel are provably co-resident (occupancy query
 //     x CU count, with the margin MI355X_MICROARCH.md prescribes where the API over-reports);
 //     every kernel whose workgroups wait for each other sizes its exchanging grid with it.
+//   * allow_dyn_lds(): raises a kernel's dynamic-LDS limit beyond 64 KiB, once per kernel and device.
 //   * tune_get()/rlvi_tune_set(): integer knobs, default <- environment <- rlvi_tune_set().
 #include <stdlib.h>
 #include <string.h>
@@ -123,6 +124,29 @@ int coop_cap_cached(const void *kernel, int block_threads, size_t dyn_lds) {
     const int sharers = tune_get("RLVI_DEVICE_SHARERS", 1);
     if (sharers > 1) cap /= sharers;
     return (forced > 0 && forced < cap) ? forced : cap;
+}
+
+namespace {
+struct LdsEntry { const void *kernel; int dev; size_t bytes; };
+constexpr int MAX_LDS = 256;
+LdsEntry g_lds[MAX_LDS];
+int g_nlds = 0;
+}  // namespace
+
+int allow_dyn_lds_cached(const void *kernel, size_t bytes) {
+    int dev = 0;
+    const hipError_t eg = hipGetDevice(&dev);
+    if (eg != hipSuccess) return (int)eg;
+    std::lock_guard<std::mutex> lk(g_mu);
+    LdsEntry *hit = nullptr;
+    for (int i = 0; i < g_nlds; ++i)
+        if (g_lds[i].kernel == kernel && g_lds[i].dev == dev) hit = &g_lds[i];
+    if (hit != nullptr && hit->bytes >= bytes) return 0;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return (int)e;
+    if (hit != nullptr) hit->bytes = bytes;
+    else if (g_nlds < MAX_LDS) g_lds[g_nlds++] = LdsEntry{kernel, dev, bytes};      // (a full table only asks again)
+    return 0;
 }
 
 }  // namespace rlvi

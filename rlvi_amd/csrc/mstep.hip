@@ -31,11 +31,7 @@ __device__ __forceinline__ void write_partial(double *part, double ta, double th
                                               double inv_rows100, int accum) {
     double *p = part + (size_t)PART_STRIDE * blockIdx.x;
     const double v0 = ta * (double)inv_scale, v1 = th * inv_rows100;
-#ifndef RLVI_MSTEP_ATOMIC_TAIL
-#define RLVI_MSTEP_ATOMIC_TAIL 1
-#endif
-    if (accum && !RLVI_MSTEP_ATOMIC_TAIL) { p[0] += v0; p[1] += v1; p[2] += ta; p[3] += th; }
-    else if (accum) {
+    if (accum) {
         // four no-return fp64 adds at the memory side instead of a read-modify-write: the record's old
         // value never travels, so the last workgroups of a launch end with four posted operations and not
         // with a load round trip (~1 us) on the launch's critical path.  One adder per record and launch,
@@ -346,10 +342,8 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
 // ---------------------------------------------------------------------------------------
 // Wave-tile form (dense rows): every WAVE streams its own tiles of R = 64/G rows through its own
 // slice of LDS -- no workgroup barrier anywhere, and the hot loop is straight-line code:
-//   A  label / index (asm loads the compiler does not count), then the tile global -> LDS by
-//      LDS-DMA (global_load_lds_dwordx4: flat, 16 B per lane, 1 KiB per wave instruction, no
-//      staging registers); the wait for "all but the DMA pieces" hands over label / index while
-//      the tile is still in flight, so the dependent pi gather flies beside the tile
+//   A  label / index, then the tile global -> registers -> LDS as flat nontemporal 16-B/lane loads
+//      (1 KiB per wave instruction); the pi gather is issued once the tile has landed
 //   B  G-lane groups own the rows as in the other forms.  A lane's slots past the end of the row
 //      alias the row's LAST vector: they read what its owner reads (harmless for the maximum),
 //      are masked out of the sum, and their in-place gradient write repeats the owner's value --
@@ -357,22 +351,11 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
 //      lanes of the group write the same value)
 //   C  flat nontemporal 16-B/lane stores LDS -> grad
 // Only full tiles; the launcher hands the B mod R trailing rows to the register-row kernel.
+// (Staging the tile by LDS-DMA, global_load_lds_dwordx4, instead of nontemporal register loads + ds_write
+// measured slower at 65 536 x 100, 12.3 against 10.4 us: a CU accepts DMA pieces only about as fast as they
+// return, so the last workgroup of a CU issues its reads 3 us after the first, while register loads of all
+// 16 waves of a CU are in flight at once.)
 // ---------------------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) const void gptr_t;
-typedef __attribute__((address_space(3))) void lptr_t;
-// RLVI_MSTEP_DMA=1: stage the tile by LDS-DMA (global_load_lds_dwordx4) instead of nontemporal
-// register loads + ds_write.  Measured slower at 65 536 x 100 (12.3 against 10.4 us): a CU accepts
-// DMA pieces only about as fast as they return, so the last workgroup of a CU issues its reads 3 us
-// after the first, while register loads of all 16 waves of a CU are in flight at once.
-#ifndef RLVI_MSTEP_DMA
-#define RLVI_MSTEP_DMA 0
-#endif
-#ifndef RLVI_MSTEP_EARLY_PI
-#define RLVI_MSTEP_EARLY_PI 0
-#endif
-#ifndef RLVI_MSTEP_DMA_AUX
-#define RLVI_MSTEP_DMA_AUX 2      // cache policy of the tile DMA: 2 = nt (read once)
-#endif
 // -DRLVI_MSTEP_STAMPS: diagnostic build, every wave leaves wall-clock stamps (100 MHz) of its first
 // tile's phases in the workspace scratch (tools/mstep_stamps.py); never in the product library.
 #ifdef RLVI_MSTEP_STAMPS
@@ -387,15 +370,14 @@ typedef __attribute__((address_space(3))) void lptr_t;
 struct FMaxF { __device__ __forceinline__ float operator()(float a, float b) const { return __builtin_fmaxf(a, b); } };
 
 // EXACT: the host guarantees ceil(ceil(C/V)/G) == KMAX, so only a lane's LAST slot can lie past
-// the end of the row and (for 16-byte vectors) only the last DMA / store piece can be partial.
+// the end of the row and (for 16-byte vectors) only the last load / store piece can be partial.
 template <typename T, int V, int G, int KMAX, int WPB, bool EXACT>
 __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_kernel(
     const T *__restrict__ logits, const int64_t *__restrict__ labels,
     const int64_t *__restrict__ idx, const float *__restrict__ weights,
     float *__restrict__ residuals, int64_t N, int64_t nfull, int C, float inv_scale,
     const float *__restrict__ grad_scale, T *__restrict__ grad, double *__restrict__ part,
-    int32_t *__restrict__ status, int accum, double inv_rows100, int hold_ticks, int gen_ticks, unsigned long long *__restrict__ hold_slot,
-    unsigned long long hold_key, int hold_cap, int hold_pct) {
+    int32_t *__restrict__ status, int accum, double inv_rows100, int hold_ticks, int gen_ticks) {
     constexpr int R = WAVE / G;                                   // rows per wave tile
     constexpr int VB = V * (int)sizeof(T);                        // bytes of a lane vector
     constexpr int NI = (KMAX * VB + 15) / 16;                     // 1-KiB pieces per tile (max)
@@ -453,18 +435,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     // read / write stream (5.4 TB/s instead of 6.5 read-only), and the write burst that follows the read
     // phase is absorbed by the Infinity Cache and drains while the next launch is being dispatched:
     // 11.15 -> 10.5 us per launch at 65 536 x 100 (hold 4.0 us; 3.0 and 6.0 us are both slower than none).
-    const unsigned long long t_begin = (hold_ticks > 0 || hold_slot != nullptr) ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    // Self-timed form (hold_slot != nullptr; what a chip-filling one-tile-per-wave launch takes by default): the
-    // hold is not an estimate of anybody's -- it is how long the PREVIOUS launch of this shape on this workspace
-    // needed to get its tile loads ISSUED, chip-wide (the issue is back-pressured by what the memory system
-    // returns, so "the last load is in flight" is when the read phase is as good as over; the per-CU barrier of
-    // the 16-wave form waits for exactly that moment, per CU).  A few waves of the launch's last workgroups --
-    // the ones a CU starts last -- leave (time bucket << 24 | ticks from their own start to their last load's
-    // issue) in the slot with one no-return atomic max: a later launch's stamps supersede an earlier one's, inside
-    // a launch the latest bucket's largest value stays.  Logits from the Infinity Cache get their loads issued
-    // sooner, so their hold is shorter by itself: no caller hint, no fitted rate.
-    unsigned long long slot_key = 0ull, slot_val = 0ull, t_issued = 0ull;
-    if (hold_slot != nullptr) { slot_key = hold_slot[0]; slot_val = hold_slot[1]; }
+    const unsigned long long t_begin = hold_ticks > 0 ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
     // CUWIDE (WPB == 16: ONE workgroup per CU, all of its 16 waves): a workgroup barrier right behind the ISSUE
     // of a wave's tile loads -- no wave of the CU sends a store into the CU's memory pipeline before every wave
@@ -481,63 +452,31 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
         const int64_t row_base = t * R;
         // ---- A
         const char *src = reinterpret_cast<const char *>(logits + row_base * C);
-        int64_t y64, ix;
-        bool okrow = true;
-        float pi;
-#if RLVI_MSTEP_DMA
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(y64) : "v"(sub8), "s"(labels + row_base) : "memory");
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(ix) : "v"(sub8), "s"(idxp + row_base) : "memory");
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t *)(src + dma_off[i]), (lptr_t *)(wtile + i * 1024), 16, 0,
-                                             RLVI_MSTEP_DMA_AUX);
-        RLVI_STAMP(1);
-        // vmcnt(NI): everything older than the NI DMA pieces (= label and index) has returned
-        asm volatile("s_waitcnt vmcnt(%2)" : "+v"(y64), "+v"(ix) : "n"(NI) : "memory");
-        ix = idx != nullptr ? ix : row_base + sub;
-        if (y64 < 0 || y64 >= C) { y64 = 0; okrow = false; }
-        if (ix < 0 || ix >= N) { ix = 0; okrow = false; }
-        pi = weights != nullptr ? weights[ix] : 1.0f;             // flies beside the tile
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(pi) : : "memory");   // tile and pi landed
-#else
         // label and index first (they return ahead of the tile: loads return in order), the tile's
         // NI chunks per lane behind them
-        y64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(labels + row_base) + sub8);
-        ix = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(idxp + row_base) + sub8);
+        int64_t y64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(labels + row_base) + sub8);
+        int64_t ix = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(idxp + row_base) + sub8);
         vu4 stg[NI];
 #pragma unroll
         for (int i = 0; i < NI; ++i)
             stg[i] = __builtin_nontemporal_load(reinterpret_cast<const vu4 *>(src + dma_off[i]));
         RLVI_STAMP(1);
-        if (hold_slot != nullptr) {
-            __builtin_amdgcn_sched_barrier(0);       // (the loads are issued, THEN the clock is read)
-            t_issued = __builtin_amdgcn_s_memrealtime();
-            __builtin_amdgcn_sched_barrier(0);
-        }
         if (CUWIDE) {
             __builtin_amdgcn_sched_barrier(0);       // (the loads are issued, THEN the barrier)
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
         }
+        bool okrow = true;
         ix = idx != nullptr ? ix : row_base + sub;
         if (y64 < 0 || y64 >= C) { y64 = 0; okrow = false; }
         if (ix < 0 || ix >= N) { ix = 0; okrow = false; }
-#if RLVI_MSTEP_EARLY_PI
-        pi = weights != nullptr ? weights[ix] : 1.0f;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) tile16[i * WAVE + lane] = stg[i];
-#else
         // the tile first, the gather once it has landed: 64 K random 4-byte reads queued beside the
         // streaming reads cost the launch 1 us (12.0 against 11.0 us at 65 536 x 100); issued here they
         // are L2 hits on a quiet queue and fly during the first half of phase B
 #pragma unroll
         for (int i = 0; i < NI; ++i) tile16[i * WAVE + lane] = stg[i];
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(y64), "+v"(ix) : : "memory");
-        if (hold_slot != nullptr && hold_pct < 0) t_issued = __builtin_amdgcn_s_memrealtime();      // (lab: "landed")
-        pi = weights != nullptr ? weights[ix] : 1.0f;
-#endif
-#endif
+        float pi = weights != nullptr ? weights[ix] : 1.0f;
         RLVI_STAMP(2);
         bad = bad || !okrow;
         __builtin_amdgcn_wave_barrier();
@@ -631,30 +570,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
         __builtin_amdgcn_wave_barrier();
         RLVI_STAMP(5);
 
-        // ---- C: flat store of the gradient tile
-#ifndef RLVI_MSTEP_NT_STORE
-#define RLVI_MSTEP_NT_STORE 1
-#endif
-#if RLVI_MSTEP_NT_STORE
-#define RLVI_TILE_STORE(val, ptr) __builtin_nontemporal_store(val, ptr)
-#else
-#define RLVI_TILE_STORE(val, ptr) (*(ptr) = (val))
-#endif
-        if (hold_slot != nullptr) {
-            const int pct = hold_pct < 0 ? -hold_pct : hold_pct;
-            long long h = slot_key == hold_key ? (long long)(slot_val & 0xFFFFFFull) * pct / 100 : 0ll;
-            h = h > hold_cap ? hold_cap : h;
-            while ((long long)(__builtin_amdgcn_s_memrealtime() - t_begin) < h) __builtin_amdgcn_s_sleep(4);
-            // the reporters: the last wave of every 16th workgroup of the launch's last quarter
-            if (lane == 0 && wave == WPB - 1 && (blockIdx.x & 15u) == 15u && blockIdx.x * 4u >= gridDim.x * 3u) {
-                unsigned long long dt = t_issued - t_begin;
-                dt = dt > 0xFFFFFFull ? 0xFFFFFFull : dt;
-                typedef __attribute__((address_space(1))) unsigned long long gull;
-                __hip_atomic_store((gull *)hold_slot, hold_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_max((gull *)(hold_slot + 1), ((t_issued >> 6) << 24) | dt, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        // ---- C: flat nontemporal store of the gradient tile
         if (hold_ticks > 0) {
             while (__builtin_amdgcn_s_memrealtime() - t_begin < (unsigned long long)hold_ticks)
                 __builtin_amdgcn_s_sleep(4);
@@ -668,11 +584,11 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 if (EXACT16 && i < NI - 1) {
-                    RLVI_TILE_STORE(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
+                    __builtin_nontemporal_store(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
                 } else if ((i + 1) * WAVE <= nchunk) {
-                    RLVI_TILE_STORE(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
+                    __builtin_nontemporal_store(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
                 } else if (i * WAVE + lane < nchunk) {
-                    RLVI_TILE_STORE(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
+                    __builtin_nontemporal_store(st[i], reinterpret_cast<vu4 *>(gdst + dma_off[i]));
                 }
             }
         }
@@ -865,9 +781,6 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
 // 13.6 MB bf16 -> 2.4 us, 16.8 MB -> 2.9, 19.7 MB -> 3.4, 26.2 MB -> 4.3, 33.5 MB -> 5.2): 0.68 us of ramp-up
 // + bytes / 7.25 TB/s; within +-0.3 us of the best hold most of the gain stays, 1 us off is worse than
 // none.  Below 12 MB no hold was found to help (the launch is over before the phases could separate).
-#ifndef RLVI_MSTEP_AUTO_DEFAULT
-#define RLVI_MSTEP_AUTO_DEFAULT 0
-#endif
 static inline int mstep_hold_ticks(double bytes) {
     if (bytes < 12.0e6) return 0;
     return (int)((0.68 + bytes / 7.25e6) * 100.0);
@@ -879,168 +792,180 @@ __global__ __launch_bounds__(256) void mstep_finalize_kernel(double *__restrict_
     reduce_partials(part, nblocks, scale, out, clear != 0, 256);
 }
 
+// The launcher's knobs (tests and the committed sweep scripts set them), read once per call.
+struct MstepKnobs {
+    int form;        // RLVI_MSTEP_FORM: see launch_mstep
+    int force_g;     // RLVI_MSTEP_G: lanes per row, 0 = the dispatch rules decide
+    int wpc;         // RLVI_MSTEP_WPC: waves per CU that stride over the wave tiles
+    int cuwide;      // RLVI_MSTEP_CUWIDE: the 16-wave barrier form where its conditions hold
+    int hold, gen;   // RLVI_MSTEP_HOLD, RLVI_MSTEP_GEN: see launch_mstep
+};
+
+// One M-step call: the caller's (checked) arguments and what every form derives from them, filled once by
+// mstep_entry and handed down by reference.
+template <typename T>
+struct MstepCall {
+    const T *logits;
+    int64_t ld;
+    const int64_t *labels, *idx;
+    const float *weights;
+    float *residuals;
+    int64_t N, B;
+    int C;
+    float inv_scale;
+    const float *grad_scale;
+    T *grad;
+    int64_t ldg;
+    float *out;
+    void *ws;
+    hipStream_t st;
+    MstepKnobs knobs;
+    // (a call with `out` has records of its own: it never touches what an accumulate sequence has piled up)
+    double *part;
+    int32_t *status;
+    int accum;                // no `out`: accumulate for rlvi_epoch_end_f32
+    double inv_rows100;
+    int cus;
+
+    // Workgroups of `wpb` waves for `tiles` wave tiles: `wpc` waves per CU stride over the tiles (one tile each
+    // at the bench size), and every workgroup owns a record
+    int64_t tile_grid(int64_t tiles, int wpb) const {
+        int64_t nb = (tiles + wpb - 1) / wpb;
+        int64_t cap = ((int64_t)knobs.wpc * cus + wpb - 1) / wpb;
+        if (cap > MSTEP_MAX_BLOCKS) cap = MSTEP_MAX_BLOCKS;
+        return nb > cap ? cap : nb;
+    }
+    // The register-row kernel over the rows from `first` on, in `nb` workgroups.  Behind a tile form (first > 0):
+    // the trailing rows, one workgroup adding to record 0
+    template <int V, int G, int KMAX>
+    int rows(int64_t first, int64_t nb) const {
+        const int kact = ((C + V - 1) / V + G - 1) / G;
+        return launch(mstep_kernel<T, V, G, KMAX>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
+                      logits + first * ld, ld, labels + first, idx != nullptr ? idx + first : idx, weights,
+                      residuals, N, B - first, C, kact, inv_scale, grad_scale,
+                      grad != nullptr ? grad + first * ldg : grad, ldg, part, status, first > 0 ? 1 : accum,
+                      inv_rows100, first);
+    }
+    // What follows a tile form's launch (rc) over `done` rows in `nb` workgroups: the trailing rows, then as finish()
+    template <int V, int G, int KMAX>
+    int tail_and_finish(int rc, int64_t done, int64_t nb) const {
+        if (rc == 0 && done < B) rc = rows<V, G, KMAX>(done, 1);
+        return finish(rc, nb);
+    }
+    // The caller's `out` from the `nb` records of the launch (rc) before
+    int finish(int rc, int64_t nb) const {
+        if (rc != 0 || out == nullptr) return rc;
+        // the finalize pass clears what it read: records are all-zero outside an accumulate sequence
+        return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
+    }
+};
+
+// mstep_wave_kernel<T, V, G, KMAX, WPB, exact> over `nfull` tiles in `nb` workgroups
+template <typename T, int V, int G, int KMAX, int WPB>
+static int launch_wave(const MstepCall<T> &c, bool exact, int64_t nb, int64_t nfull, int hold_ticks, int gen_ticks) {
+    constexpr size_t LDS = (size_t)WPB * ((KMAX * V * sizeof(T) + 15) / 16) * 1024;
+    auto go = [&](auto kern) {
+        if constexpr (WPB == 16) {      // (> 64 KiB of dynamic LDS)
+            if (const int e = allow_dyn_lds(kern, LDS)) return e;
+        }
+        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), LDS, c.st, c.logits, c.labels, c.idx, c.weights,
+                      c.residuals, c.N, nfull, c.C, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,
+                      c.inv_rows100, hold_ticks, gen_ticks);
+    };
+    return exact ? go(mstep_wave_kernel<T, V, G, KMAX, WPB, true>) : go(mstep_wave_kernel<T, V, G, KMAX, WPB, false>);
+}
+
 template <typename T, int V, int G, int KMAX>
-static int launch_mstep(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
-                        const float *weights, float *residuals, int64_t N, int64_t B, int C,
-                        int kact, float inv_scale, const float *grad_scale, T *grad, int64_t ldg, float *out,
-                        void *ws, hipStream_t st) {
+static int launch_mstep(const MstepCall<T> &c) {
     constexpr int R = WAVE / G;
     constexpr int WPB = 4;                          // waves per workgroup of the wave-tile form
-    const int cus = device_info().cus;
+    const int64_t B = c.B;
+    const int C = c.C;
     // form: 1 = wave tiles through LDS (dense rows), 0 = register rows everywhere; -1 (default): wave tiles
     // once the launch has more than two waves per CU (512 tiles) -- below that a call is one wave's latency
     // long, and global -> registers -> global is shorter than the trip through LDS (tools/sweep_small.sh:
     // 4096 x 10 3.4 -> 3.1 us, 4096 x 100 4.05 -> 3.7; 16 384 x 100 the other way, 5.2 against 5.7)
-    int form = tune_get("RLVI_MSTEP_FORM", -1);
+    int form = c.knobs.form;
     if (form < 0) form = (B + R - 1) / R > 512 ? 1 : 0;
-    char *base = static_cast<char *>(ws);
-    // (a call with `out` has records of its own: it never touches what an accumulate sequence has piled up)
-    double *part = reinterpret_cast<double *>(base + (out == nullptr ? WS_PART_OFF : WS_PART2_OFF));
-    int32_t *status = reinterpret_cast<int32_t *>(base);
-    const int accum = out == nullptr ? 1 : 0;       // no `out`: accumulate for rlvi_epoch_end_f32
-    const double inv_rows100 = 100.0 / (double)B;
-    const bool flat16 = ld == C && (grad == nullptr || ldg == C) &&
-                        ((uintptr_t)logits % 16) == 0 && ((uintptr_t)grad % 16) == 0;
+    const bool flat16 = c.ld == C && (c.grad == nullptr || c.ldg == C) &&
+                        ((uintptr_t)c.logits % 16) == 0 && ((uintptr_t)c.grad % 16) == 0;
     const size_t wtile_bytes = (size_t)R * C * sizeof(T);
     constexpr size_t SKB = (size_t)((KMAX * V * sizeof(T) + 15) / 16);
     const bool dense_wave = flat16 && wtile_bytes % 16 == 0 && wtile_bytes / 16 <= SKB * WAVE;
-    int64_t nb;
-    int rc;
     const int64_t nfull = B / R;
-    if (dense_wave && form >= 1 && nfull > 0) {
-        // `wpc` waves per CU stride over the R-row tiles (one tile each at the bench size)
-        const int wpc = tune_get("RLVI_MSTEP_WPC", 16);
-        nb = (nfull + WPB - 1) / WPB;
-        int64_t cap = ((int64_t)wpc * cus + WPB - 1) / WPB;
-        if (cap > MSTEP_MAX_BLOCKS) cap = MSTEP_MAX_BLOCKS;
-        if (nb > cap) nb = cap;
-        // (RLVI_MSTEP_LDS_PAD: extra LDS per workgroup = fewer resident workgroups per CU; with the grid
-        //  uncapped the dispatcher then hands the remaining tiles to whichever CU frees up first)
-        const size_t lds = (size_t)WPB * SKB * 1024 + (size_t)tune_get("RLVI_MSTEP_LDS_PAD", 0);
-        // reads-then-writes hold (see the kernel): only when no wave has a second tile and a gradient is
-        // written.  RLVI_MSTEP_HOLD = ticks of 10 ns; 0 (the default): off; -1: from the bytes the launch
-        // reads AT THE HBM READ RATE -- for logits that stream from HBM (a block that is not resident in the
-        // Infinity Cache: bench.py's rotation of twelve blocks, a block larger than the cache).  Logits that
-        // the model's last layer has just written are served by the cache, their read phase is over sooner
-        // than the hold assumes, and the hold then COSTS time (single buffer pair: 9.4 -> 10.3 us): the
-        // caller knows which case it is in, the kernel does not (a per-CU barrier between reads and writes
-        // -- 16-wave workgroups -- was built to let the data decide: no gain cold, 9.4 -> 10.1 us warm).
-        // (the caller's hint lives with the caller's workspace -- rlvi_workspace_set_option(ws, "logits_from_hbm", 1)
-        //  -- not with the process: two training loops, or two streams, do not see each other's; the knob of the
-        //  same meaning is the lab override)
-        int hold_ticks = tune_get("RLVI_MSTEP_HOLD", ws_option(ws, WSOPT_LOGITS_FROM_HBM, 0) ? -1 : 0);
-        int gen_ticks = tune_get("RLVI_MSTEP_GEN", -1);      // ticks between the holds of successive tile generations
-        const int64_t waves = nb * WPB;
-        const double gen_bytes = (double)(nfull < waves ? nfull : waves) * (double)wtile_bytes;
-        if (nfull > waves && hold_ticks < 0 && gen_ticks < 0) {
-            // several tiles per wave under the caller's HBM hint: one hold per GENERATION of tiles, the
-            // generations one read + one write of their bytes at the mixed rate apart (2 x 26.2 MB: 9.0 us).
-            // Only where it was measured to pay (tools/sweep_gen.sh): fp32, two to four FULL generations
-            // (65 536 x 100 per generation: 21.8 -> 20.0 us at two, 30.6 -> 29.3 at three, 39.8 -> 39.0 at four;
-            // five gain or lose a per cent with the spacing, a half-filled last generation or eight lose)
-            const int64_t gens = nfull / waves;
-            gen_ticks = (sizeof(T) == 4 && nfull % waves == 0 && gens >= 2 && gens <= 4 && gen_bytes >= 12.0e6)
-                            ? (int)(2.0 * gen_bytes / 5.76e6 * 100.0) : 0;
-        }
-        if (gen_ticks < 0) gen_ticks = 0;
-        if (grad == nullptr || (nfull > waves && gen_ticks <= 0 && hold_ticks < 0)) hold_ticks = 0;
-        if (hold_ticks < 0) hold_ticks = mstep_hold_ticks(gen_bytes);
-        if (hold_ticks == 0) gen_ticks = 0;
-        // the self-timed hold (see the kernel): a chip-filling launch with one tile per wave that writes a gradient
-        // and reads at least 12 MB (below that no hold was found to help), unless the caller or the lab said
-        // something else.  RLVI_MSTEP_AUTO=0: the 16-wave barrier form of round 3 instead.
-        unsigned long long *hold_slot = nullptr;
-        unsigned long long hold_key = 0ull;
-        int hold_cap = 0;
-        const int hold_pct = tune_get("RLVI_MSTEP_AUTO_PCT", 100);
-        if (tune_get("RLVI_MSTEP_AUTO", RLVI_MSTEP_AUTO_DEFAULT) && grad != nullptr && hold_ticks == 0 &&
-            nfull <= waves && gen_bytes >= 12.0e6) {
-            hold_key = ((unsigned long long)nfull << 32) ^ ((unsigned long long)C * sizeof(T) << 8) ^ (unsigned)WPB;
-            WsHeader *hdr = reinterpret_cast<WsHeader *>(base);
-            hold_slot = &hdr->mstep_hold[(unsigned)((nfull * 31 + C * (int)sizeof(T)) & 3)][0];
-            hold_cap = mstep_hold_ticks(gen_bytes) * 3 / 2;      // (a stamp of a descheduled wave must not stall a launch)
-        }
-        bool cuwide_done = false;
-        if constexpr (G == 4 && V * sizeof(T) == 16) {
-            constexpr int WPB16 = 16;
-            int64_t nb16 = (nfull + WPB16 - 1) / WPB16;
-            // (a caller that has hinted HBM-resident logits gets the four-wave workgroups with the timed hold:
-            //  10.65 against 10.95 us -- the timed hold separates the phases chip-wide, the barrier per CU)
-            if (tune_get("RLVI_MSTEP_CUWIDE", 1) && grad != nullptr && hold_ticks == 0 && hold_slot == nullptr &&
-                nb16 <= cus &&
-                nb16 * 5 >= (int64_t)cus * 4 && nb16 <= MSTEP_MAX_BLOCKS) {
-                const size_t lds16 = (size_t)WPB16 * SKB * 1024;
-                auto go = [&](auto kern) {
-                    static int attr_dev = -1;      // (> 64 KiB of dynamic LDS: asked for once per kernel and device)
-                    int cur_dev = 0;
-                    if (hipGetDevice(&cur_dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-                    if (attr_dev != cur_dev) {
-                        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-                        if (e != hipSuccess) return (int)e;
-                        attr_dev = cur_dev;
-                    }
-                    return launch(kern, dim3((unsigned)nb16), dim3(WPB16 * WAVE), lds16, st, logits, labels, idx,
-                                  weights, residuals, N, nfull, C, inv_scale, grad_scale, grad, part, status, accum,
-                                  inv_rows100, hold_ticks, 0, (unsigned long long *)nullptr, 0ull, 0, 100);
-                };
-                rc = kact == KMAX ? go(mstep_wave_kernel<T, V, G, KMAX, WPB16, true>)
-                                  : go(mstep_wave_kernel<T, V, G, KMAX, WPB16, false>);
-                nb = nb16;
-                cuwide_done = true;
-                ws_note_mstep(ws, 3);
-            }
-        }
-        if (!cuwide_done) ws_note_mstep(ws, 2 + (hold_ticks != 0 ? 16 : 0) + (hold_slot != nullptr ? 32 : 0));
-        if (cuwide_done) {
-        } else if (kact == KMAX)
-            rc = launch(mstep_wave_kernel<T, V, G, KMAX, WPB, true>, dim3((unsigned)nb), dim3(WPB * WAVE),
-                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad_scale,
-                        grad, part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap,
-                        hold_pct);
-        else
-            rc = launch(mstep_wave_kernel<T, V, G, KMAX, WPB, false>, dim3((unsigned)nb), dim3(WPB * WAVE),
-                        lds, st, logits, labels, idx, weights, residuals, N, nfull, C, inv_scale, grad_scale,
-                        grad, part, status, accum, inv_rows100, hold_ticks, gen_ticks, hold_slot, hold_key, hold_cap,
-                        hold_pct);
-        const int64_t done = nfull * R;
-        if (rc == 0 && done < B) {
-            // the B mod R trailing rows: one workgroup of the register-row kernel, adding to record 0
-            rc = launch(mstep_kernel<T, V, G, KMAX>, dim3(1), dim3(MSTEP_THREADS), 0, st,
-                        logits + done * ld, ld, labels + done, idx != nullptr ? idx + done : idx, weights,
-                        residuals, N, B - done, C, kact, inv_scale, grad_scale,
-                        grad != nullptr ? grad + done * ldg : grad, ldg, part, status, 1, inv_rows100, done);
-        }
-    } else {
-        const int max_blocks = tune_get("RLVI_MSTEP_BLOCKS", MSTEP_MAX_BLOCKS);
+    if (!(dense_wave && form >= 1 && nfull > 0)) {
         const int64_t rows_per_block = (int64_t)MSTEP_WAVES * R;
-        nb = (B + rows_per_block - 1) / rows_per_block;
-        if (nb > max_blocks) nb = max_blocks;
+        int64_t nb = (B + rows_per_block - 1) / rows_per_block;
         if (nb > MSTEP_MAX_BLOCKS) nb = MSTEP_MAX_BLOCKS;
         if (nb < 1) nb = 1;
-        ws_note_mstep(ws, 1);
-        rc = launch(mstep_kernel<T, V, G, KMAX>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                    logits, ld, labels, idx, weights, residuals, N, B, C, kact, inv_scale, grad_scale, grad,
-                    ldg, part, status, accum, inv_rows100, (int64_t)0);
+        ws_note_mstep(c.ws, 1);
+        return c.finish(c.template rows<V, G, KMAX>(0, nb), nb);
     }
-    if (rc != 0 || out == nullptr) return rc;
-    // the finalize pass clears what it read: records are all-zero outside an accumulate sequence
-    return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
+    // (extra LDS per workgroup -- fewer resident workgroups per CU, the dispatcher then hands the remaining tiles
+    //  to whichever CU frees up first -- measured slower: DESIGN.md 3.1)
+    int64_t nb = c.tile_grid(nfull, WPB);
+    // reads-then-writes hold (see the kernel): only when no wave has a second tile and a gradient is
+    // written.  RLVI_MSTEP_HOLD = ticks of 10 ns; 0 (the default): off; -1: from the bytes the launch
+    // reads AT THE HBM READ RATE -- for logits that stream from HBM (a block that is not resident in the
+    // Infinity Cache: bench.py's rotation of twelve blocks, a block larger than the cache).  Logits that
+    // the model's last layer has just written are served by the cache, their read phase is over sooner
+    // than the hold assumes, and the hold then COSTS time (single buffer pair: 9.4 -> 10.3 us): the
+    // caller knows which case it is in, the kernel does not (a per-CU barrier between reads and writes
+    // -- 16-wave workgroups -- was built to let the data decide: no gain cold, 9.4 -> 10.1 us warm).
+    // (the caller's hint lives with the caller's workspace -- rlvi_workspace_set_option(ws, "logits_from_hbm", 1)
+    //  -- not with the process: two training loops, or two streams, do not see each other's; the knob of the
+    //  same meaning is the lab override)
+    int hold_ticks = c.knobs.hold;
+    int gen_ticks = c.knobs.gen;      // ticks between the holds of successive tile generations
+    const int64_t waves = nb * WPB;
+    const double gen_bytes = (double)(nfull < waves ? nfull : waves) * (double)wtile_bytes;
+    if (nfull > waves && hold_ticks < 0 && gen_ticks < 0) {
+        // several tiles per wave under the caller's HBM hint: one hold per GENERATION of tiles, the
+        // generations one read + one write of their bytes at the mixed rate apart (2 x 26.2 MB: 9.0 us).
+        // Only where it was measured to pay (tools/sweep_gen.sh): fp32, two to four FULL generations
+        // (65 536 x 100 per generation: 21.8 -> 20.0 us at two, 30.6 -> 29.3 at three, 39.8 -> 39.0 at four;
+        // five gain or lose a per cent with the spacing, a half-filled last generation or eight lose)
+        const int64_t gens = nfull / waves;
+        gen_ticks = (sizeof(T) == 4 && nfull % waves == 0 && gens >= 2 && gens <= 4 && gen_bytes >= 12.0e6)
+                        ? (int)(2.0 * gen_bytes / 5.76e6 * 100.0) : 0;
+    }
+    if (gen_ticks < 0) gen_ticks = 0;
+    if (c.grad == nullptr || (nfull > waves && gen_ticks <= 0 && hold_ticks < 0)) hold_ticks = 0;
+    if (hold_ticks < 0) hold_ticks = mstep_hold_ticks(gen_bytes);
+    if (hold_ticks == 0) gen_ticks = 0;
+    const bool exact = ((C + V - 1) / V + G - 1) / G == KMAX;
+    int rc = 0;
+    bool cuwide = false;
+    if constexpr (G == 4 && V * sizeof(T) == 16) {
+        constexpr int WPB16 = 16;
+        const int64_t nb16 = (nfull + WPB16 - 1) / WPB16;
+        // (a caller that has hinted HBM-resident logits gets the four-wave workgroups with the timed hold:
+        //  10.65 against 10.95 us -- the timed hold separates the phases chip-wide, the barrier per CU)
+        cuwide = c.knobs.cuwide && c.grad != nullptr && hold_ticks == 0 && nb16 <= c.cus &&
+                 nb16 * 5 >= (int64_t)c.cus * 4 && nb16 <= MSTEP_MAX_BLOCKS;
+        if (cuwide) {
+            nb = nb16;
+            ws_note_mstep(c.ws, 3);
+            rc = launch_wave<T, V, G, KMAX, WPB16>(c, exact, nb, nfull, 0, 0);
+        }
+    }
+    if (!cuwide) {
+        ws_note_mstep(c.ws, 2 + (hold_ticks != 0 ? 16 : 0));
+        rc = launch_wave<T, V, G, KMAX, WPB>(c, exact, nb, nfull, hold_ticks, gen_ticks);
+    }
+    return c.template tail_and_finish<V, G, KMAX>(rc, nfull * R, nb);
 }
 
 // Picks the lane group: the smallest G whose lanes need at most 8 vectors each (so the short
 // DPP reductions are amortised over up to 8*V elements per lane); rows of <= 8 vectors are
 // handled by a single lane.
 template <typename T, int V>
-static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
-                       const float *weights, float *residuals, int64_t N, int64_t B, int C,
-                       float inv_scale, const float *grad_scale, T *grad, int64_t ldg, float *out, void *ws,
-                       hipStream_t st) {
+static int dispatch_gk(const MstepCall<T> &c) {
+    const int64_t B = c.B;
+    const int C = c.C;
     const int nv = (C + V - 1) / V;
-    const int force_g = tune_get("RLVI_MSTEP_G", 0);
-#define RLVI_CASE(G_, K_)                                                                        \
-    return launch_mstep<T, V, G_, K_>(logits, ld, labels, idx, weights, residuals, N, B, C,      \
-                                      (nv + G_ - 1) / G_, inv_scale, grad_scale, grad, ldg, out, ws, st)
+    const int force_g = c.knobs.force_g;
+#define RLVI_CASE(G_, K_) return launch_mstep<T, V, G_, K_>(c)
     // (bf16 in 16-byte vectors: at most FOUR vectors = 32 elements per lane, as fp32's eight -- with 64 elements a lane's
     //  serial work and its registers cost more than the shorter reductions save: tools/lab/sweep_g_bf16.sh, 16 384 x 256
     //  11.2 -> 6.5 us, x 512 15.8 -> 8.6, x 1000 24.3 -> 15.8, x 2000 39.5 -> 26.7, 4096 x 1000 10.8 -> 6.6)
@@ -1069,12 +994,11 @@ static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const
             if constexpr (V == 1) RLVI_CASE(4, 32);
         }
         // the same for rows of 129 ... 512 such elements (Places365's 365 classes): sixteen lanes per row, four rows per
-        // wave tile, instead of one row per wave in single 4-byte loads (lab knob RLVI_MSTEP_ODD16=0: the old route)
+        // wave tile, instead of one row per wave in single 4-byte loads
         // -- 65 536 x 365 fp32 46.0 -> 39.5 us, 16 384 x 365 15.5 -> 11.8, 65 536 x 201 27.9 -> 22.1, 65 536 x 366 bf16
         // 30.9 -> 24.4; not below 8192 rows (4096 x 365: 5.9 against 7.2) and not beyond 24 single elements per lane (x 511:
         // 54.6 against 58.0, the 32-slot form spills)
-        if (gsel > 16 && C > 128 && C <= 512 && !force_g && B >= tune_get("RLVI_MSTEP_ODD16_ROWS", 8192) &&
-            tune_get("RLVI_MSTEP_ODD16", 1)) {
+        if (gsel > 16 && C > 128 && C <= 512 && !force_g && B >= 8192) {
             const int k16 = (nv + 15) / 16;
             if constexpr (!(sizeof(T) == 2 && V == 4)) {         // (bf16 in 8-byte vectors never has gsel > 16 here)
                 if (k16 <= 16) RLVI_CASE(16, 16);
@@ -1096,23 +1020,17 @@ static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const
     const int k = (nv + gsel - 1) / gsel;
     if (k > 8) {
         // more than 512 vectors per row: a wave (or, for few rows, a workgroup) per row, three passes (mstep_longrow_kernel)
-        char *base = static_cast<char *>(ws);
-        double *part = reinterpret_cast<double *>(base + (out == nullptr ? WS_PART_OFF : WS_PART2_OFF));
         // fewer rows than four per CU: the whole workgroup on one row
-        const bool wide = B <= 4 * (int64_t)device_info().cus;
+        const bool wide = B <= 4 * (int64_t)c.cus;
         int64_t nb = wide ? B : (B + MSTEP_WAVES - 1) / MSTEP_WAVES;
         if (nb > MSTEP_MAX_BLOCKS) nb = MSTEP_MAX_BLOCKS;
-        ws_note_mstep(ws, 5);
-        const int rc = wide ? launch(mstep_longrow_kernel<T, V, MSTEP_WAVES>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad,
-                                     ldg, part,
-                                     reinterpret_cast<int32_t *>(base), out == nullptr ? 1 : 0, 100.0 / (double)B)
-                            : launch(mstep_longrow_kernel<T, V, 1>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                                     logits, ld, labels, idx, weights, residuals, N, B, C, inv_scale, grad_scale, grad,
-                                     ldg, part,
-                                     reinterpret_cast<int32_t *>(base), out == nullptr ? 1 : 0, 100.0 / (double)B);
-        if (rc != 0 || out == nullptr) return rc;
-        return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
+        ws_note_mstep(c.ws, 5);
+        auto go = [&](auto kern) {
+            return launch(kern, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, c.st, c.logits, c.ld, c.labels, c.idx,
+                          c.weights, c.residuals, c.N, B, C, c.inv_scale, c.grad_scale, c.grad, c.ldg, c.part, c.status,
+                          c.accum, c.inv_rows100);
+        };
+        return c.finish(wide ? go(mstep_longrow_kernel<T, V, MSTEP_WAVES>) : go(mstep_longrow_kernel<T, V, 1>), nb);
     }
     switch (gsel) {
         case 1:
@@ -1135,6 +1053,26 @@ static int dispatch_gk(const T *logits, int64_t ld, const int64_t *labels, const
 #undef RLVI_CASE
 }
 
+// The word-wise wave tile (mstep_bf16w_kernel); the B mod 16 trailing rows go to the register-row kernel.
+template <typename T>
+static int launch_bf16w(const MstepCall<T> &c) {
+    constexpr int WPB = 4;
+    const int64_t nfull = c.B / 16;
+    const int64_t nb = c.tile_grid(nfull, WPB);
+    const size_t lds = (size_t)WPB * (4 * 1024 + 64);
+    const int kw = ((c.C + 3) / 4 + 1) / 2;        // words of a lane's segment of ceil(C / 4) elements
+    ws_note_mstep(c.ws, 4);
+    auto go = [&](auto kern) {
+        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), lds, c.st, c.logits, c.labels, c.idx, c.weights,
+                      c.residuals, c.N, nfull, c.C, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,
+                      c.inv_rows100);
+    };
+    const int rc = kw <= 8    ? go(mstep_bf16w_kernel<T, 8, WPB>)
+                   : kw <= 13 ? go(mstep_bf16w_kernel<T, 13, WPB>)
+                              : go(mstep_bf16w_kernel<T, 16, WPB>);
+    return c.template tail_and_finish<1, 16, 8>(rc, nfull * 16, nb);
+}
+
 template <typename T>
 static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const int64_t *idx,
                        const float *weights, float *residuals, int64_t N, int64_t B, int64_t C,
@@ -1149,65 +1087,39 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
         ((uintptr_t)residuals & 3) || ((uintptr_t)out & 3) || ((uintptr_t)ws & 255) || ((uintptr_t)grad_scale & 3) ||
         ((uintptr_t)logits % sizeof(T)) || (grad && ((uintptr_t)grad % sizeof(T))))
         return RLVI_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *base = static_cast<char *>(ws);
+    MstepCall<T> c;
+    c.logits = logits; c.ld = ld; c.labels = labels; c.idx = idx; c.weights = weights; c.residuals = residuals;
+    c.N = N; c.B = B; c.C = (int)C; c.inv_scale = inv_scale; c.grad_scale = grad_scale; c.grad = grad; c.ldg = ldg;
+    c.out = out; c.ws = ws; c.st = static_cast<hipStream_t>(stream);
+    c.knobs.form = tune_get("RLVI_MSTEP_FORM", -1);
+    c.knobs.force_g = tune_get("RLVI_MSTEP_G", 0);
+    c.knobs.wpc = tune_get("RLVI_MSTEP_WPC", 16);
+    c.knobs.cuwide = tune_get("RLVI_MSTEP_CUWIDE", 1);
+    c.knobs.hold = tune_get("RLVI_MSTEP_HOLD", ws_option(ws, WSOPT_LOGITS_FROM_HBM, 0) ? -1 : 0);
+    c.knobs.gen = tune_get("RLVI_MSTEP_GEN", -1);
+    c.part = reinterpret_cast<double *>(base + (out == nullptr ? WS_PART_OFF : WS_PART2_OFF));
+    c.status = reinterpret_cast<int32_t *>(base);
+    c.accum = out == nullptr ? 1 : 0;
+    c.inv_rows100 = 100.0 / (double)B;
+    c.cus = device_info().cus;
     // widest vector for which every row start and the row length are aligned
     auto ok = [&](int v) { return vec_fits<T>(v, C, {{logits, ld}, {grad, ldg}}); };
     constexpr int VMAX = 16 / (int)sizeof(T);
-    const int Ci = (int)C;
     if constexpr (sizeof(T) == 2) {
         // bf16 / fp16 rows of an odd number of elements (single 2-byte elements in the general forms), at least
-        // 32 768 of them, dense, 16-byte aligned: the word-wise wave tile (mstep_bf16w_kernel); the B mod 16
-        // trailing rows go to the register-row kernel.  (Every 2-byte decision here and in dispatch_gk was tuned on
-        // bytes, not on the format: fp16 takes the form bf16 takes at every shape.)
-        if (((C & 1) != 0 || tune_get("RLVI_MSTEP_BF16W", 1) == 2) && C >= 9 && C <= 127 && B >= 16 * 2048 && ld == C && (grad == nullptr || ldg == C) &&
-            ((uintptr_t)logits % 16) == 0 && ((uintptr_t)grad % 16) == 0 && tune_get("RLVI_MSTEP_BF16W", 1) &&
-            tune_get("RLVI_MSTEP_FORM", -1) != 0 && tune_get("RLVI_MSTEP_G", 0) == 0) {
-            constexpr int WPB = 4;
-            char *base = static_cast<char *>(ws);
-            double *part = reinterpret_cast<double *>(base + (out == nullptr ? WS_PART_OFF : WS_PART2_OFF));
-            int32_t *status = reinterpret_cast<int32_t *>(base);
-            const int accum = out == nullptr ? 1 : 0;
-            const double inv_rows100 = 100.0 / (double)B;
-            const int64_t nfull = B / 16;
-            int64_t nb = (nfull + WPB - 1) / WPB;
-            int64_t cap = ((int64_t)tune_get("RLVI_MSTEP_WPC", 16) * device_info().cus + WPB - 1) / WPB;
-            if (cap > MSTEP_MAX_BLOCKS) cap = MSTEP_MAX_BLOCKS;
-            if (nb > cap) nb = cap;
-            const size_t lds = (size_t)WPB * (4 * 1024 + 64);
-            const int L = (Ci + 3) / 4;
-            const int kw = (L + 1) / 2;
-            int rc;
-            ws_note_mstep(ws, 4);
-#define RLVI_BW(KW_)                                                                                       \
-    rc = launch(mstep_bf16w_kernel<T, KW_, WPB>, dim3((unsigned)nb), dim3(WPB * WAVE), lds, st, logits, labels,    \
-                idx, weights, residuals, N, nfull, Ci, inv_scale, grad_scale, grad, part, status, accum, inv_rows100)
-            if (kw <= 8) RLVI_BW(8);
-            else if (kw <= 13) RLVI_BW(13);
-            else RLVI_BW(16);
-#undef RLVI_BW
-            const int64_t done = nfull * 16;
-            if (rc == 0 && done < B)
-                rc = launch(mstep_kernel<T, 1, 16, 8>, dim3(1), dim3(MSTEP_THREADS), 0, st, logits + done * ld, ld,
-                            labels + done, idx != nullptr ? idx + done : idx, weights, residuals, N, B - done, Ci,
-                            (Ci + 15) / 16, inv_scale, grad_scale, grad != nullptr ? grad + done * ldg : grad, ldg,
-                            part, status, 1, inv_rows100, done);
-            if (rc != 0 || out == nullptr) return rc;
-            return launch(mstep_finalize_kernel, dim3(1), dim3(256), 0, st, part, (int)nb, 1.0, out, 1);
-        }
+        // 32 768 of them, dense, 16-byte aligned: the word-wise wave tile.  (Every 2-byte decision here and in
+        // dispatch_gk was tuned on bytes, not on the format: fp16 takes the form bf16 takes at every shape.)
+        if ((C & 1) != 0 && C >= 9 && C <= 127 && B >= 16 * 2048 && ld == C && (grad == nullptr || ldg == C) &&
+            ((uintptr_t)logits % 16) == 0 && ((uintptr_t)grad % 16) == 0 && c.knobs.form != 0 && c.knobs.force_g == 0)
+            return launch_bf16w(c);
     }
     if constexpr (VMAX == 8) {
-        if (ok(8))
-            return dispatch_gk<T, 8>(logits, ld, labels, idx, weights, residuals, N, B, Ci,
-                                     inv_scale, grad_scale, grad, ldg, out, ws, st);
+        if (ok(8)) return dispatch_gk<T, 8>(c);
     }
-    if (ok(4))
-        return dispatch_gk<T, 4>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                                 grad_scale, grad, ldg, out, ws, st);
-    if (ok(2))
-        return dispatch_gk<T, 2>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                                 grad_scale, grad, ldg, out, ws, st);
-    return dispatch_gk<T, 1>(logits, ld, labels, idx, weights, residuals, N, B, Ci, inv_scale,
-                             grad_scale, grad, ldg, out, ws, st);
+    if (ok(4)) return dispatch_gk<T, 4>(c);
+    if (ok(2)) return dispatch_gk<T, 2>(c);
+    return dispatch_gk<T, 1>(c);
 }
 
 }  // namespace rlvi

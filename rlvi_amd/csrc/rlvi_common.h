@@ -52,6 +52,13 @@ template <class K>
 inline int coop_cap(K kernel, int block_threads, size_t dyn_lds = 0) {
     return coop_cap_cached(reinterpret_cast<const void *>(kernel), block_threads, dyn_lds);
 }
+// A launch of `kernel` with more than 64 KiB of dynamic LDS has to be allowed first
+// (hipFuncAttributeMaxDynamicSharedMemorySize): asked for once per (kernel, device); 0 or the HIP error code.
+int allow_dyn_lds_cached(const void *kernel, size_t bytes);
+template <class K>
+inline int allow_dyn_lds(K kernel, size_t bytes) {
+    return allow_dyn_lds_cached(reinterpret_cast<const void *>(kernel), bytes);
+}
 // Launch with the launch's OWN return code (hipLaunchKernel), not the process-wide sticky error:
 // a stale error of somebody else's call is neither reported as ours nor cleared for its owner.
 template <typename... KArgs, size_t... I>
@@ -81,11 +88,7 @@ struct WsHeader {
     uint32_t pad1[63];
     uint32_t epoch_base;     // tag base of the exchange slots (advanced by every coop kernel)
     uint32_t pad2[63];
-    // self-timed reads-then-writes hold of the M-step (mstep.hip): four slots {shape key, (time bucket << 24) | ticks}
-    // -- how long the LAST launch of that shape took to get its tile loads issued, chip-wide; the next launch holds
-    // its stores that long
-    unsigned long long mstep_hold[4][2];
-    uint32_t pad3[48];
+    uint32_t pad3[64];
 };
 constexpr size_t WS_HDR_BYTES = sizeof(WsHeader);                       // 1024
 static_assert(sizeof(WsHeader) == 1024, "the header ends where the exchange slots begin");

@@ -693,16 +693,7 @@ extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int6
     const size_t lds = ((size_t)2 * npad_x + (size_t)SL_NW * 3 * 256 + 2 * SL_DP * SL_GPITCH + 3 * SL_DP +
                         2 * SL_NW * 2 + 2 + ((res && two) ? 1024 * 8 : 0)) * sizeof(double);
     auto go = [&](auto kern) {
-        // (> 64 KiB of dynamic LDS: asked for once per kernel and device)
-        static int attr_dev = -1;
-        int cur = 0;
-        if (hipGetDevice(&cur) != hipSuccess) return (int)hipErrorInvalidDevice;
-        if (attr_dev != cur) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_dev = cur;
-        }
+        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
         return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d, npad_x, maxiter, tol,
                       estep_tol, estep_maxiter, theta, weights, info,
                       reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF));

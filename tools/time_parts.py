@@ -17,7 +17,7 @@ ap.add_argument("--rows", type=int, default=65536)
 ap.add_argument("--classes", type=int, default=100)
 ap.add_argument("--n", type=int, default=0, help="E-step / threshold vector length (default rows)")
 ap.add_argument("--steps", type=int, default=200)
-ap.add_argument("--dtype", default="f32")
+ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
 ap.add_argument("--tag", default="")
 ap.add_argument("--seq-idx", action="store_true", help="sample indices in order instead of a permutation (lab: what the random gather / scatter costs)")
 ap.add_argument("--tune", action="append", default=[], help="NAME=VALUE knob (rlvi_tune_set); repeatable")
@@ -29,9 +29,10 @@ N = a.n or B
 d0, labels, idx, logits, grads, weights, residuals = bench.make_inputs(torch, dev, B, C, B, 0)
 if a.seq_idx:
     idx = torch.arange(B, device=dev, dtype=torch.int64)
-if a.dtype == "bf16":
-    logits = [z.to(torch.bfloat16) for z in logits]
-    grads = [g.to(torch.bfloat16) for g in grads]
+if a.dtype in ("bf16", "f16"):
+    tdt = torch.bfloat16 if a.dtype == "bf16" else torch.float16
+    logits = [z.to(tdt) for z in logits]
+    grads = [g.to(tdt) for g in grads]
 if N != B:
     from rlvi_amd import synth
     residuals_n = torch.from_numpy(synth.residual_vector("bimodal", N, 1)).to(dev)
@@ -109,7 +110,7 @@ with torch.cuda.stream(side):
     def describe(best):
         extra = ""
         if a.what in ("mstep", "mstep_warm", "mstep_fwd", "mstep_out"):
-            s = 2 if a.dtype == "bf16" else 4
+            s = 2 if a.dtype in ("bf16", "f16") else 4
             byt = B * ((1 if a.what == "mstep_fwd" else 2) * C * s + 24)
             extra = f" {byt / best / 1e3:8.1f} GB/s  frac {byt / best / 1e3 / 8000:.3f}"
         if a.what in ("estep", "fused", "step"):
@@ -126,10 +127,6 @@ with torch.cuda.stream(side):
         sys.exit(0)
     best = time_leg()
     extra = describe(best)
-    if any(t.startswith("RLVI_MSTEP_AUTO=1") for t in a.tune):
-        import numpy as np
-        hs = ws.buf[768:768 + 64].cpu().numpy().view(np.uint64).reshape(4, 2)
-        print("   hold slots (key, ticks of 10 ns):", [(hex(int(k)), int(v) & 0xFFFFFF) for k, v in hs if k])
     if a.what in ("thr", "thr_fn") and any(t.startswith("RLVI_THR_DEBUG") for t in a.tune):
         import numpy as np
         off = ops.debug_scratch_offset() + 256
