@@ -321,6 +321,44 @@ int rlvi_jocor_bwd_f16(const uint16_t *logits1, int64_t ld1, const uint16_t *log
                        uint16_t *grad2, int64_t ldg2, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * CDR's gradient masking over all weight tensors of a network.  Replaces deep-learning/methods/train_cdr.py:22-44:
+ * the torch.cat of every covered gradient and parameter (:22-29), metric = |g * v| (:30), torch.topk(metric, nz)
+ * read for its last value (:33-34) and, per tensor, mask = (|v * g| >= thresh) * clip; g = mask * g (:40-44) --
+ * without a concatenated copy and without a sort: the nz-th largest metric is found to the bit by a radix descent
+ * (11 + 10 + 10 bits) on the metric's bit pattern, over a table of segments, one per tensor.  The result equals the
+ * reference's bit for bit (fp32 products commute, `>=` keeps every tie); a NaN metric orders above +inf.
+ *
+ *   rlvi_cdr_table_bytes(nseg)    bytes of the segment table (host copy and device copy alike); 0 for nseg < 1
+ *   rlvi_cdr_table_fill           HOST only, touches no device (train_cdr.py:24-27, the walk over the parameters):
+ *       writes the table of segments {v[i], g[i], n[i], first chunk} into host_buf (8-byte aligned,
+ *       rlvi_cdr_table_bytes(nseg) bytes); v[i] / g[i] are DEVICE pointers to n[i] contiguous fp32 values, 4-byte
+ *       alignment is enough.  *total = sum n[i] (:31), *chunks = the fixed-size pieces of work all segments make.
+ *       The caller uploads host_buf to 16-byte-aligned device memory, so that the launch below never copies.
+ *       RLVI_E_NULL for a null pointer (an entry of v / g included), RLVI_E_SHAPE for nseg < 1 or an n[i] < 1,
+ *       RLVI_E_ALIGN for a v[i] / g[i] that is not 4-byte aligned.
+ *   rlvi_cdr_scratch_bytes(nseg)  bytes of device scratch for the histograms and the state of the descent
+ *       (16-byte aligned, any contents; apart from the workspace, whose layout it leaves alone)
+ *   rlvi_cdr_mask_f32             (train_cdr.py:30-44) five launches whatever nseg is:
+ *       table_dev  the uploaded table;  nseg, total, chunks  as rlvi_cdr_table_fill gave them
+ *       nz         int(nonzero_ratio * total) of the caller (:32), 1 <= nz <= total (the reference raises an
+ *                  IndexError for nz == 0: the caller's to raise)
+ *       clip       the scale of the kept gradients (:43)
+ *       thr_out    device fp32: the nz-th largest |g * v| (:34)
+ *       kept_out   device int64: entries with |g * v| >= *thr_out (>= nz; more when values tie at the threshold)
+ *       every g[i] is overwritten with m * g[i], m = clip where |g[i] * v[i]| >= *thr_out, else 0.0f -- as that
+ *       multiplication: a dropped entry keeps its sign on its zero, a dropped infinite gradient becomes NaN.
+ *       RLVI_E_NULL / RLVI_E_SHAPE (nseg < 1, nz < 1, nz > total, chunks outside [nseg, total]) / RLVI_E_ALIGN (table
+ *       or scratch not 16-byte aligned, thr_out, kept_out) / RLVI_E_WS (scratch_bytes too small) / RLVI_E_LIMIT
+ *       (total >= 2^32), all before any launch.
+ * ------------------------------------------------------------------------------------- */
+size_t rlvi_cdr_table_bytes(int nseg);
+int rlvi_cdr_table_fill(void *host_buf, const void *const *v, void *const *g, const int64_t *n, int nseg,
+                        int64_t *total, int64_t *chunks);
+size_t rlvi_cdr_scratch_bytes(int nseg);
+int rlvi_cdr_mask_f32(const void *table_dev, int nseg, int64_t total, int64_t chunks, int64_t nz, float clip,
+                      void *scratch, size_t scratch_bytes, float *thr_out, int64_t *kept_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * precision@k.  Replaces accuracy(logit, target, topk) of deep-learning/utils.py:65-79 (softmax :67, torch.topk
  * :70, eq :72, the per-k counts :76-77): hits[j] = number of rows whose label is among the ks[j]
  * largest logits of its row, j < nk <= 8.  train_rlvi keeps only precision@1 (train_rlvi.py:85), which the

@@ -767,3 +767,117 @@ def jocor_loss(logits1, logits2, labels, forget_rate, co_lambda=0.1, ws=None, ou
     if check:
         ws.raise_on_status("jocor_loss")
     return loss
+
+
+def cdr_covered(params):
+    """The tensors CDR's mask covers (train_cdr.py:25,:41): those with dim() in (2, 4), in the order given."""
+    return [p for p in params if p.dim() in (2, 4)]
+
+
+def cdr_num_nonzero(nonzero_ratio, total):
+    """nz of train_cdr.py:32: int(nonzero_ratio * num_params), on whatever float type the caller holds (rate_schedule
+    holds np.float64).  IndexError for nz == 0, where the reference's top_values[-1] (:34) raises it."""
+    nz = int(nonzero_ratio * total)
+    if nz == 0:
+        raise IndexError("index -1 is out of bounds for dimension 0 with size 0")
+    return nz
+
+
+class CdrMasker:
+    """CDR's gradient masking of train_cdr.py:22-44 over a fixed list of parameters, in five launches per call whatever
+    their number: masker(nonzero_ratio, clip) finds thr = the int(nonzero_ratio * total)-th largest |p.grad * p| over
+    ALL covered parameters by a radix descent (no concatenated copy, no sort: rlvi_amd/csrc/cdr.hip) and overwrites
+    every covered p.grad with ((|p * p.grad| >= thr) * clip) * p.grad -- the reference's bits.
+
+    `params`: the parameters in named_parameters() order; those with dim() in (2, 4) are covered, the others are left
+    alone.  The masker owns a pinned host table of {p, p.grad, numel} per covered tensor, its device copy, the
+    scratch of the descent and the two outputs.  The table is refilled and uploaded only when a data_ptr() changed
+    since the last call (optimizer.zero_grad() sets the gradients to None, so backward allocates them anew; the
+    caching allocator usually hands the same addresses back); `uploads` counts how often that happened."""
+
+    def __init__(self, params):
+        L = _lib.load()
+        self.params = cdr_covered(list(params))
+        if not self.params:
+            raise ValueError("CdrMasker: no parameter with dim() in (2, 4)")
+        _require_gpu(*self.params)
+        for p in self.params:
+            if p.dtype != torch.float32:
+                raise TypeError("CdrMasker: fp32 parameters only (the reference has no other; AMP keeps them fp32)")
+            if not p.is_contiguous():
+                raise ValueError("CdrMasker: a covered parameter is not contiguous")
+        dev = self.params[0].device
+        if any(p.device != dev for p in self.params):
+            raise ValueError("CdrMasker: parameters on more than one device")
+        self.nseg = len(self.params)
+        self.total = sum(p.numel() for p in self.params)
+        if any(p.numel() < 1 for p in self.params):
+            raise ValueError("CdrMasker: an empty parameter")
+        nbytes = int(L.rlvi_cdr_table_bytes(self.nseg))
+        self._host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        self._table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._scratch = torch.empty(int(L.rlvi_cdr_scratch_bytes(self.nseg)), dtype=torch.uint8, device=dev)
+        assert self._table.data_ptr() % 16 == 0 and self._scratch.data_ptr() % 16 == 0
+        self.thr = torch.zeros((), dtype=torch.float32, device=dev)
+        self.kept = torch.zeros((), dtype=torch.int64, device=dev)
+        self._n = (ctypes.c_int64 * self.nseg)(*[p.numel() for p in self.params])
+        self._ptrs = None
+        self._uploaded = None               # event behind the last upload: the host table is free again after it
+        self.chunks = 0
+        self.uploads = 0
+
+    def _pointers(self):
+        """The addresses of every covered parameter and gradient, as the table holds them.  This runs on every call,
+        so it looks at no more than the call could not do without: a gradient that is there and contiguous."""
+        grads = []
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                raise ValueError("CdrMasker: a covered parameter has no gradient (run backward first)")
+            if not g.is_contiguous():
+                raise ValueError("CdrMasker: a gradient is not contiguous")
+            grads.append(g.data_ptr())
+        return tuple([p.data_ptr() for p in self.params] + grads)
+
+    def _refresh(self, ptrs):
+        L = _lib.load()
+        for p in self.params:                # an address changed: look at the tensors behind them properly
+            g = p.grad
+            if g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape:
+                raise ValueError("CdrMasker: a gradient is not an fp32 tensor of its parameter's shape and device")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("CdrMasker: a covered parameter is no longer a contiguous fp32 tensor")
+        if self._uploaded is not None:
+            self._uploaded.synchronize()
+        v = (ctypes.c_void_p * self.nseg)(*ptrs[:self.nseg])
+        g = (ctypes.c_void_p * self.nseg)(*ptrs[self.nseg:])
+        total, chunks = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(L.rlvi_cdr_table_fill(ctypes.c_void_p(self._host.data_ptr()), v, g, self._n, self.nseg,
+                                         ctypes.byref(total), ctypes.byref(chunks)), "rlvi_cdr_table_fill")
+        assert total.value == self.total
+        self.chunks = chunks.value
+        self._table.copy_(self._host, non_blocking=True)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+        self._ptrs = ptrs
+        self.uploads += 1
+
+    def __call__(self, nonzero_ratio, clip):
+        """Mask the gradients in place; returns (thr, kept) as 0-dim device tensors (fp32, int64) owned by the masker
+        and overwritten by its next call.  No host synchronisation.  IndexError for int(nonzero_ratio * total) == 0,
+        where the reference's top_values[-1] raises it."""
+        nz = cdr_num_nonzero(nonzero_ratio, self.total)
+        ptrs = self._pointers()
+        if ptrs != self._ptrs:
+            self._refresh(ptrs)
+        rc = _lib.load().rlvi_cdr_mask_f32(_ptr(self._table), self.nseg, self.total, self.chunks, nz, float(clip),
+                                           _ptr(self._scratch), self._scratch.numel(), _ptr(self.thr),
+                                           _ptr(self.kept), _stream_ptr())
+        _lib.check(rc, "rlvi_cdr_mask_f32")
+        return self.thr, self.kept
+
+
+def cdr_mask_(params, nonzero_ratio, clip):
+    """One-shot form of CdrMasker: mask the gradients of `params` in place, return (thr, kept).  A training loop keeps
+    a CdrMasker instead (its table survives from step to step)."""
+    return CdrMasker(params)(nonzero_ratio, clip)
