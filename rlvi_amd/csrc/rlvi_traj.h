@@ -34,6 +34,17 @@ struct TjOut {
     alignas(16) float coef[TJ_MAXK + 2][8];
 };
 
+// Hand-over between the recurrence wave and the wave that runs the guessed-pair half of the acceptance test
+// beside the serial chain (first round with the fourth-order sums, tj_accept_guess below).  One slot per lane,
+// used in both directions: the recurrence wave leaves {r'_k, err'_k} and `steps` before the first barrier, the
+// helper overwrites its own lane's slots with {1 / |h'_k|, ln rbar'_k, slope_k} before the second.
+struct TjSplit {
+    float rn_ihq[TJ_MAXK];
+    float err_lrq[TJ_MAXK];
+    float slope[TJ_MAXK];
+    int steps;
+};
+
 // Neighbour lanes and an affine scan over the 64 lanes without the LDS crossbar (a __shfl is a
 // ds_bpermute, ~100 cycles of latency each, and the recurrence is one long dependent chain).
 __device__ __forceinline__ float lane_up1(float v) {      // lane i <- lane i-1 (lane 0 <- 0)
@@ -87,6 +98,47 @@ __device__ __forceinline__ void wave_sort_keys(float &key, int &src) {
     }
 }
 
+// The half of the acceptance test (tj_chain below, "Accept WITHOUT a verification round") that needs only the
+// GUESSED pairs and this round's totals: ln rbar' and ln P' of every pair, the secant slopes, 1 / |h'|.  Three
+// logarithms, three reciprocals and two ballots that do not wait for the chain, so a second wave runs them
+// while the recurrence wave is in its serial chain (a lone wave issues one vector instruction per ~6 clocks
+// whatever it depends on: nothing can be tucked into the chain's stalls on the SAME wave).  The expressions
+// are the ones tj_chain had, operand for operand; every lane of the helper wave calls, between the two
+// workgroup barriers of tj_chain<true, true, true>.
+__device__ __forceinline__ void tj_accept_guess(TjSplit &sp, int xstep, unsigned long long *dbg) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & (WAVE - 1);
+    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[996] = wall_clock64();
+    const float rn = sp.rn_ihq[lane];
+    const float err_l = sp.err_lrq[lane];
+    const int steps = __builtin_amdgcn_readfirstlane(sp.steps);
+    const bool live = lane < steps;                                      // (steps <= Ke: has && lane < steps)
+    const float rp_old = lane_up1(rn);
+    const float hq = rn - rp_old;                                        // guessed step
+    const float rbarq = 0.5f * (rn + rp_old);
+    const float lrq = __logf(fmaxf(rbarq, 1e-30f));
+    const float lpq = 2.0f * (__logf(fmaxf(err_l, 1e-30f)) - __logf(fmaxf(fabsf(hq), 1e-30f)));   // ln P'
+    const bool pair = live && lane >= 1;
+    // slope of ln P against ln rbar: secant to the previous pair where that is at least 2 % away,
+    // else (pairs crowding at a fixed point) the secant from the last pair to the nearest one that is
+    const float lrq_p = lane_up1(lrq), lpq_p = lane_up1(lpq);
+    const float lr_last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lrq), steps - 1));
+    const float lp_last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lpq), steps - 1));
+    const unsigned long long far = __ballot(pair && fabsf(lrq - lr_last) >= 0.02f);
+    const int jstar = far ? 63 - (int)__builtin_clzll(far) : 1;
+    const float lr_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lrq), jstar));
+    const float lp_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lpq), jstar));
+    const float slope_c = far ? (lp_j - lp_last) * __builtin_amdgcn_rcpf(lr_j - lr_last) : 0.0f;
+    const float slope_own = (lane >= 2 && fabsf(lrq - lrq_p) >= 0.02f) ? (lpq - lpq_p) * __builtin_amdgcn_rcpf(lrq - lrq_p)
+                                                                       : slope_c;
+    const float slope = fminf(fmaxf(slope_own, -6.0f), 2.0f);
+    const float ihq = __builtin_amdgcn_rcpf(fmaxf(fabsf(hq), 1e-30f));
+    sp.rn_ihq[lane] = ihq;
+    sp.err_lrq[lane] = lrq;
+    sp.slope[lane] = slope;
+    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[997] = wall_clock64();
+}
+
 // ---------------------------------------------------------------------------------------
 // The recurrence of train_rlvi.py:30-37 on one wave.  Lane j holds node j: its guess rn_l and the
 // totals tS = S(rn), tP = dS/dr(rn), tQ = -1/2 d2S/dr2(rn) (0: first-order correction only),
@@ -99,14 +151,18 @@ __device__ __forceinline__ void wave_sort_keys(float &key, int &src) {
 // ---------------------------------------------------------------------------------------
 // HI (first round of estep_trajb.hip): tR3 = sum e^3/(1+re)^4 and tR4 = sum e^4/(1+re)^5 (the third- and
 // fourth-order terms of S around the node) are given too; the chain then runs on the fourth-order
-// model and may ACCEPT THE ROUND WITHOUT A VERIFICATION ROUND (see below).
+// model and may ACCEPT THE ROUND WITHOUT A VERIFICATION ROUND (see below).  HI takes TWO WORKGROUP BARRIERS,
+// whatever the data: one behind the operand table, one in front of the acceptance test; between them another wave
+// of the workgroup runs tj_accept_guess on `sp` and every remaining wave just passes the two barriers
+// (trajb_solve).
 template <bool FIRST, bool HASQ = true, bool HI = false>
 __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, float tP, float tQ,
                                          float tD,
                                          float gmin, bool dead, float rn_l, float shift, float invN,
                                          float tol, float *trace, bool want_nodes, int xstep,
                                          unsigned long long *dbg, float tR3 = 0.0f, float tR4 = 0.0f,
-                                         bool cold = false) {
+                                         bool cold = false, TjSplit *sp = nullptr) {
+    static_assert(!HI || FIRST, "the fourth-order sums are taken in the first round only");
     const int lane = threadIdx.x & (WAVE - 1);
     const bool has = lane < Ke;
     // RLVI_TJ_DEBUG: where the recurrence wave's time goes (first round of workgroup 0)
@@ -179,6 +235,18 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
             avg_l = fmaf(b_l * rn, eps, a0_l);
         }
     }
+    if (HI) {
+        // the chain's operand table, what the helper wave needs, and the first of the two barriers: outside every
+        // condition on the data (a dead workgroup and a round that will not be accepted pass it all the same)
+        float *cf = out.coef[lane];
+        *reinterpret_cast<float4 *>(cf) = make_float4(rn, a0_l, b_l, c_l);
+        *reinterpret_cast<float2 *>(cf + 4) = make_float2(r3_l, r4_l);
+        if (lane == 0) *reinterpret_cast<float4 *>(out.coef[TJ_MAXK]) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+        sp->rn_ihq[lane] = rn;
+        sp->err_lrq[lane] = err_l;
+        if (lane == 0) sp->steps = steps;
+        __syncthreads();
+    }
     TJ_STAMP(1);   // lane-parallel preparation done
     // serial chain; `step` is wave-uniform, so the per-node values come through v_readlane
     // (SGPR lane select, no LDS):  avg = a0 + b d - c d^2, d = r - r',  r <- avg / (1 - avg).
@@ -194,14 +262,8 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
         if (HI) {
             // Fourth-order chain.  S(r' + d) = S + S' d - Q d^2 + R3 d^3 - R4 d^4 + ...  (alternating for
             // d > 0, terms falling by a factor <= |d|/r').  The arithmetic of a step is what it always was
-            // (Estrin: three dependent levels behind dr); its six per-node operands now come through LDS.
-            {
-                float *cf = out.coef[lane];
-                *reinterpret_cast<float4 *>(cf) = make_float4(rn, a0_l, b_l, c_l);
-                *reinterpret_cast<float2 *>(cf + 4) = make_float2(r3_l, r4_l);
-                if (lane == 0) *reinterpret_cast<float4 *>(out.coef[TJ_MAXK]) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-            }
-            __builtin_amdgcn_wave_barrier();
+            // (Estrin: three dependent levels behind dr); its six per-node operands now come through LDS
+            // (the table was written in front of the barrier above).
             // two register sets, two steps per trip: the operands of step k + 1 are asked for BEFORE the
             // arithmetic of step k, so the LDS latency (~100 clocks) runs beside a step instead of in front of
             // every one (written out by hand: with one set and a copy the compiler rotates the loop and the
@@ -380,9 +442,17 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
     // 3 x sqrt2 E r/|h| + 2 x {2 mv^2 + |sigma dln rbar|/4 + 0.5 %}; anything inside a band: no
     // accept, the verification round runs.
     TJ_STAMP(3);   // trust check / tail done
+    // (the second barrier: the helper wave's half of the test is in `sp` behind it -- long since, it is a tenth
+    //  of the chain)
+    if (HI) __syncthreads();
+    if ((RLVI_STAMPS && dbg != nullptr) && HI && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[998] = wall_clock64();
     int it_acc = 0;
     bool accept_now = false;
     if (HI && FIRST && __all(inside) && !scanned && round_ok && trace == nullptr && steps >= 2) {
+        // (no implicit contraction in here: with the guessed-pair half gone to another wave the compiler would be
+        //  free to fuse other products and sums than it did while both halves were one block; the one fused
+        //  multiply-add it did form -- in `band` -- is written out)
+#pragma clang fp contract(off)
         const bool live = has && lane < steps;
         const float dk = rnew_l - rn;                                        // d at this node
         const float om = 1.0f - avg_l;
@@ -404,32 +474,19 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
         const float Ekm = lane_up1(Ek);
         // the measured pairs: step, midpoint, P = D'/h'^2
         const float rp_new = lane_up1(rnew_l);
-        const float rp_old = lane_up1(rn);
-        const float h = rnew_l - rp_new, hq = rn - rp_old;                   // corrected / guessed step
-        const float rbar = 0.5f * (rnew_l + rp_new), rbarq = 0.5f * (rn + rp_old);
-        const float lrq = __logf(fmaxf(rbarq, 1e-30f));
-        const float lpq = 2.0f * (__logf(fmaxf(err_l, 1e-30f)) - __logf(fmaxf(fabsf(hq), 1e-30f)));   // ln P'
-        const bool pair = live && lane >= 1;
-        // slope of ln P against ln rbar: secant to the previous pair where that is at least 2 % away,
-        // else (pairs crowding at a fixed point) the secant from the last pair to the nearest one that is
-        const float lrq_p = lane_up1(lrq), lpq_p = lane_up1(lpq);
-        const float lr_last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lrq), steps - 1));
-        const float lp_last = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lpq), steps - 1));
-        const unsigned long long far = __ballot(pair && fabsf(lrq - lr_last) >= 0.02f);
-        const int jstar = far ? 63 - (int)__builtin_clzll(far) : 1;
-        const float lr_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lrq), jstar));
-        const float lp_j = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lpq), jstar));
-        const float slope_c = far ? (lp_j - lp_last) * __builtin_amdgcn_rcpf(lr_j - lr_last) : 0.0f;
-        const float slope_own = (lane >= 2 && fabsf(lrq - lrq_p) >= 0.02f) ? (lpq - lpq_p) * __builtin_amdgcn_rcpf(lrq - lrq_p)
-                                                                           : slope_c;
-        float slope = fminf(fmaxf(slope_own, -6.0f), 2.0f);
+        const float h = rnew_l - rp_new;                                     // corrected step
+        const float rbar = 0.5f * (rnew_l + rp_new);
+        // the guessed pairs' half (tj_accept_guess, run by another wave beside the chain): ln rbar', the slope of
+        // ln P' against ln rbar', 1 / |h'|
+        const float lrq = sp->err_lrq[lane];
+        const float slope = sp->slope[lane];
+        const float ihq = sp->rn_ihq[lane];
         const float dl = __logf(fmaxf(rbar, 1e-30f)) - lrq;                  // how far the pair moved
-        const float ihq = __builtin_amdgcn_rcpf(fmaxf(fabsf(hq), 1e-30f));
         const float err_hat = err_l * fabsf(h) * ihq * __expf(0.5f * slope * dl);
         const float mvk = adk * __builtin_amdgcn_rcpf(rn);
         const float mv = fmaxf(mvk, lane_up1(mvk));                          // relative move of the pair's nodes
         const float node_term = 1.4143f * fmaxf(Ek, Ekm) * rbar * __builtin_amdgcn_rcpf(fmaxf(fabsf(h), 1e-30f));
-        float band = 3.0f * node_term + 2.0f * (2.0f * mv * mv + 0.25f * fabsf(slope * dl) + 0.005f);
+        float band = 3.0f * node_term + 2.0f * (fmaf(2.0f * mv, mv, 0.25f * fabsf(slope * dl)) + 0.005f);
         float err_e = err_hat;
         if (lane == 0) { err_e = err_l; band = 0.0f; }                       // node 0 and the caller's pi are exact
         const bool clear = !live || (band < 0.5f && fabsf(err_e - tol) > band * err_e);

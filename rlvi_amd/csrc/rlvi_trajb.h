@@ -34,9 +34,14 @@ constexpr int TB_NSPLIT_MAXS = 1024;     // node-split up to this many samples p
 constexpr bool tb_nsplit(int E, int block) { return E * block <= TB_NSPLIT_MAXS; }
 constexpr int tb_stage(int E, int block) { return tb_nsplit(E, block) ? E * block : 4; }
 
+// The hand-over of the split acceptance test (rlvi_traj.h) exists only where the fourth-order first round does: in
+// the 256-thread geometry.  An empty base takes no room, so the fat 512-thread forms keep their LDS layout.
+template <bool ON> struct TbSplit {};
+template <> struct TbSplit<true> { TjSplit split; };
+
 // STAGE > 4 <=> node-split: then no wave partials go through LDS at all (records leave from the registers)
 template <int TB_NW, int STAGE = 4>
-struct TbShared {
+struct TbShared : TbSplit<TB_NW * WAVE == 256> {
     float wp[STAGE > 4 ? 1 : TB_NW][STAGE > 4 ? 1 : TJ_MAXK][8];     // wave partials {S, P, Q, D, R3, R4, P2, -} per node (sample-split sums)
     float pmin[TB_NW];
     double red[TB_PER][TB_NV];
@@ -251,6 +256,8 @@ __device__ __forceinline__ TbSolved trajb_solve(
     }
     TB_STAMP();   // slice loaded
 
+    TjSplit *split = nullptr;           // (only the geometry with the fourth-order first round has one)
+    if constexpr (TB_BLOCK == 256) split = &sh.split;
     const float invN = 1.0f / (float)N;
     int it = K;
     float r_fin = rn_l;
@@ -631,9 +638,9 @@ __device__ __forceinline__ TbSolved trajb_solve(
             TB_STAMP();   // totals in
             const float gm = (lane < Ke && nq > 4) ? val[4] : __builtin_inff();
             if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && round == 0) dbg[900 + lane] = ((unsigned long long)nq << 32) | __float_as_uint(val[4]);
-            if (HI_OK && hi_round)
+            if (HI_OK && hi_round)      // (two workgroup barriers inside: the other waves meet them below)
                 tj_chain<true, true, HI_OK>(sh.out, Ke, K, val[0], val[1], val[2], val[3], gm, dead, rn_l, shift,
-                                            invN, tol, trace, true, xstep, dbg, val[5], val[6]);
+                                            invN, tol, trace, true, xstep, dbg, val[5], val[6], false, split);
             else if (round == 0)
                 tj_chain<true>(sh.out, Ke, K, val[0], val[1], val[2], val[3],
                                gm, dead,
@@ -642,6 +649,17 @@ __device__ __forceinline__ TbSolved trajb_solve(
                 tj_chain<false>(sh.out, Ke, K, val[0], val[1], val[2], val[3],
                                gm, dead,
                                 rn_l, shift, invN, tol, trace, true, xstep, dbg);
+        } else if (HI_OK && hi_round) {
+            // The fourth-order first round: wave 0 is in tj_chain<true, true, true>, which passes two workgroup
+            // barriers -- behind its operand table and in front of its acceptance test.  Between them wave 1 runs
+            // the half of that test that does not wait for the chain; every other wave, the caller's spare ones
+            // included, passes the same two barriers.  hi_round is the same in every thread of the workgroup
+            // (the round, the caller's arguments, the warm-start state), and nothing between here and there
+            // depends on `dead` or on the totals: the count of barriers is the same for all waves whatever
+            // the data.
+            __syncthreads();
+            if (wave == 1) tj_accept_guess(*split, xstep, dbg);
+            __syncthreads();
         }
         __syncthreads();
         ++tag; ++xstep; ++ptag;

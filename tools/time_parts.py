@@ -171,6 +171,10 @@ with torch.cuda.stream(side):
         print("  slope  :", np.array(ee & 0xFFFFFFFF, np.uint32).view(np.float32)[:24])
         cs = full[990:996].astype(np.int64)
         print("recurrence wave [entry, prepared, chain, trust/tail, acceptance, out] us:", [round(float(v - cs[0]) / 100.0, 2) for v in cs])
+        if int(full[996]) > 0:      # (the split acceptance test: the helper wave between the recurrence wave's two barriers)
+            hs = full[996:999].astype(np.int64)
+            print("   helper wave [start, done] and the recurrence wave past its second barrier, us on the same axis:",
+                  [round(float(v - cs[0]) / 100.0, 2) for v in hs])
         if int(full[980]) > 0:
             print("sums of workgroup 0 / wave 0: arithmetic done at", round(float(int(full[980]) - int(st[0])) / 100.0, 2),
                   "butterflies done at", round(float(int(full[981]) - int(st[0])) / 100.0, 2), "us since kernel start")
