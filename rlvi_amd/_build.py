@@ -13,7 +13,10 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "librlvi_gfx950.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+# (kernarg preload: the first 14 SGPRs' worth of a kernel's arguments -- 56 bytes -- arrive with the wave instead of
+#  being fetched by it; the kernels order their arguments by first use so that the first loads need nothing else.
+#  The compiler adds a header that fetches them the old way where the firmware does not preload.)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-kernarg-preload-count=16",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 

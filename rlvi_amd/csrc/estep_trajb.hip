@@ -39,10 +39,15 @@ namespace rlvi {
 #endif
 template <int E, int TB_BLOCK>
 __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMPS) ? RLVI_TB_MINW : 1) void estep_trajb_kernel(
-    float *__restrict__ res, float *__restrict__ wts, int64_t N, float tol, int K,
-    int32_t *__restrict__ out_iters, float *__restrict__ trace, void *ws,
-    float *__restrict__ mstep_out, double mstep_scale, unsigned long long *__restrict__ dbg, int G,
-    int64_t Nall, PeerTable *__restrict__ pt, int verify) {
+    float *__restrict__ res, float *__restrict__ wts, void *ws, int64_t N, int64_t Nall, int Ls, int G, int K,
+    int flags, float tol, int32_t *__restrict__ out_iters, float *__restrict__ trace,
+    float *__restrict__ mstep_out, double mstep_scale, unsigned long long *__restrict__ dbg,
+    PeerTable *__restrict__ pt) {
+    // Argument order = order of first use: the first 56 bytes (res ... flags) are preloaded into SGPRs at wave
+    // start (rlvi_amd/_build.py: kernarg preload) and are all that the slice loads and the warm-start state's
+    // loads need; the rest is asked for in one burst and waited for once, behind those loads (the pin below).
+    // Ls: the slice length ceil(N / G), from the launcher (a 64-bit division costs every wave ~130 dependent
+    // instructions in front of its first load).  flags: TBF_* below.
     // G <= TB_G exchanging workgroups (what is provably co-resident on this device).  The epoch end's
     // reduction of the M-step records (mstep_out != nullptr) is done by workgroup G - 1 inside the solve, in
     // the time it would otherwise wait for the first round's totals -- no extra workgroup (round 2 had one:
@@ -50,19 +55,30 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     __shared__ TbShared<TB_BLOCK / WAVE, tb_stage(E, TB_BLOCK)> sh;
     const int tid = threadIdx.x;
 #if RLVI_STAMPS
-    // (lab build: shader clock of this launch = delta s_memtime / delta s_memrealtime x 100 MHz)
-    const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+    // (lab build: the wall clock as the kernel's very first instruction -- it needs no argument --, stored with the
+    //  other stamps once dbg is known: dbg[986] entry, [987] first data loads issued, [988] slice landed;
+    //  shader clock of this launch = delta s_memtime / delta s_memrealtime x 100 MHz)
+    // The compiler puts its own fetch of the arguments past the preloaded ones at the top of the kernel, in front
+    // of anything written here.  So this build does not touch those parameters: it reads them from the argument
+    // block itself, through a pointer that exists only behind the stamp (offsets = the signature's layout).
+    unsigned long long rt0;
+    typedef const __attribute__((address_space(4))) char *tb_ka_t;
+    tb_ka_t ka = (tb_ka_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("s_memrealtime %0" : "=s"(rt0));
+    asm volatile("" : "+s"(ka));
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
+    unsigned long long rt1 = 0ull;
+#define TB_ENTRY_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); rt1 = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define TB_ENTRY_STAMP(k) do { } while (0)
 #endif
     const int b = (int)blockIdx.x;
-    const int64_t L = (N + G - 1) / G;
+    const int64_t L = Ls;
     const int64_t lo = (int64_t)b * L < N ? (int64_t)b * L : N;
     const int64_t hi = lo + L < N ? lo + L : N;
-    // (sharded over several GPUs: N samples here, Nall over all ranks, pt the peers' inboxes;
-    //  otherwise Nall == N and pt == nullptr)
-    // (verify bit 1: the caller asked for a cold start -- the workspace option "cold_start": no guess from the last call)
-    const TbWarm wm = tb_warm(ws, Nall, K, pt != nullptr, (verify & 2) != 0);
 
-    // ---- slice -> registers: raw residuals and the caller's pi
+    // ---- slice -> registers: raw residuals and the caller's pi.  Issued first: they need preloaded arguments only
     float l[E], ev[E], q0[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -71,8 +87,38 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
         l[j] = ok ? res[i] : __builtin_inff();
         q0[j] = ok ? wts[i] : 0.0f;
     }
+    TB_ENTRY_STAMP(1);   // first data loads issued
+    // (sharded over several GPUs: N samples here, Nall over all ranks, pt the peers' inboxes;
+    //  otherwise Nall == N and pt == nullptr)
+    // (TBF_COLD: the caller asked for a cold start -- the workspace option "cold_start": no guess from the last call)
+    // The warm-start state's loads go out beside the slice loads (one round trip for both), and so does the
+    // request for the arguments past the preloaded ones: one wait for all of it.
+#if RLVI_STAMPS
+#define TB_LATE(T, off) (*(T const __attribute__((address_space(4))) *)(ka + (off)))
+    tol = TB_LATE(float, 56);
+    out_iters = TB_LATE(int32_t *, 64);
+    trace = TB_LATE(float *, 72);
+    mstep_out = TB_LATE(float *, 80);
+    mstep_scale = TB_LATE(double, 88);
+    dbg = TB_LATE(unsigned long long *, 96);
+    pt = TB_LATE(PeerTable *, 104);
+#undef TB_LATE
+#endif
+    TbWarmRaw raw = tb_warm_issue(ws, (flags & TBF_SHARDED) != 0);
+    asm volatile("" : "+s"(raw.n), "+s"(raw.k), "+s"(raw.it), "+s"(raw.shift)
+                 : "s"(tol), "s"(out_iters), "s"(trace), "s"(mstep_out), "s"(mstep_scale), "s"(dbg), "s"(pt));
+    const TbWarm wm = tb_warm_select<tb_early_nodes(E, TB_BLOCK)>(raw, Nall, K, (flags & TBF_COLD) != 0);
+#if RLVI_STAMPS
+    if (dbg != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+        dbg[986] = rt0;                                   // entry: the kernel's very first instruction
+        dbg[987] = rt1;                                   // first data loads issued
+        float keep = l[0] + q0[0];
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(keep) : : "memory");
+        dbg[988] = __builtin_amdgcn_s_memrealtime();      // slice landed
+    }
+#endif
     const TbSolved s = trajb_solve<E, TB_BLOCK>(sh, wm, l, q0, ev, true, b, G, Nall, tol, K, out_iters, trace,
-                                                ws, dbg, pt, (verify & 1) != 0, mstep_out, mstep_scale);
+                                                ws, dbg, pt, (flags & TBF_VERIFY) != 0, mstep_out, mstep_scale);
     // a wait that timed out (RLVI_ST_TIMEOUT: the workgroups were not all resident) leaves the
     // caller's residuals and pi as they were -- the host raises on the status; it never hands out garbage
 #if RLVI_STAMPS
@@ -115,10 +161,12 @@ int try_launch_estep_trajb(float *res, float *wts, int64_t N, float tol, int max
     unsigned long long *dbg = (debug && !dry_run) ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
     const int64_t Nall = sharded ? n_all : N;
     PeerTable *pt = (sharded && !dry_run) ? reinterpret_cast<PeerTable *>(static_cast<char *>(ws) + WS_PEER_OFF) : nullptr;
-    // bit 0: always run the verification round (lab knob); bit 1: ignore the previous call's trajectory (the
-    // caller's workspace option "cold_start": every call as the reference's loop starts it, train_rlvi.py:29)
-    const int verify = (tune_get("RLVI_TJ_VERIFY", 0) ? 1 : 0) |
-                       ((!sharded && !dry_run && ws_option(ws, WSOPT_COLD_START, 0)) ? 2 : 0);
+    // TBF_VERIFY: always run the verification round (lab knob); TBF_COLD: ignore the previous call's trajectory (the
+    // caller's workspace option "cold_start": every call as the reference's loop starts it, train_rlvi.py:29);
+    // TBF_SHARDED: the state of sharded calls (pt != nullptr in the kernel)
+    const int flags = (tune_get("RLVI_TJ_VERIFY", 0) ? TBF_VERIFY : 0) |
+                      ((!sharded && !dry_run && ws_option(ws, WSOPT_COLD_START, 0)) ? TBF_COLD : 0) |
+                      (pt != nullptr ? TBF_SHARDED : 0);
     int launched = 0;
     // The exchanging workgroups wait for each other, so all of them (and the reduction workgroup) must
     // be resident at once: a geometry (E samples per thread, B threads) runs on G = min(TB_G, what
@@ -134,10 +182,11 @@ int try_launch_estep_trajb(float *res, float *wts, int64_t N, float tol, int max
         auto kern = estep_trajb_kernel<E_, B_>;                                                   \
         int G = coop_cap(kern, B_);                                                               \
         if (G > TB_G) G = TB_G;                                                                   \
-        if (G >= TJ_MAXK && (N + G - 1) / G <= (int64_t)(E_) * (B_)) {                            \
+        const int64_t L = G > 0 ? (N + G - 1) / G : 0;   /* the slice length: the kernel divides nothing */ \
+        if (G >= TJ_MAXK && L <= (int64_t)(E_) * (B_)) {                                          \
             if (!dry_run)                                                                         \
-                *rc = launch(kern, dim3((unsigned)G), dim3(B_), 0, st, res, wts, N, tol, maxiter,           \
-                             out_iters, trace, ws, mstep_out, mstep_scale, dbg, G, Nall, pt, verify); \
+                *rc = launch(kern, dim3((unsigned)G), dim3(B_), 0, st, res, wts, ws, N, Nall, (int)L, G,    \
+                             maxiter, flags, tol, out_iters, trace, mstep_out, mstep_scale, dbg, pt); \
             else                                                                                  \
                 *rc = 0;                                                                          \
             launched = 1;                                                                         \

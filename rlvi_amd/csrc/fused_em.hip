@@ -145,9 +145,11 @@ __device__ __forceinline__ void fe_batch_scalars(float acc, float hits, const Tb
 template <int KMAX, bool EXACT>
 __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
     const float *__restrict__ logits, const int64_t *__restrict__ labels, float *__restrict__ loss_rows,
-    float *__restrict__ pi, int64_t B, int C, float inv_scale, float tol, int K,
-    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters, void *ws,
+    float *__restrict__ pi, void *ws, int64_t B, int C, int K, float inv_scale, float tol,
+    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters,
     unsigned long long *__restrict__ dbg, int G, int verify) {
+    // (argument order = order of first use: what the first loads and the warm-start state need lies in the first
+    //  56 bytes, which arrive in SGPRs at wave start -- rlvi_amd/_build.py: kernarg preload)
     constexpr int V = 4, LG = 4;                                  // floats per lane vector, lanes per row
     constexpr int NI = KMAX;                                      // 1-KiB pieces per tile (max)
     constexpr int WTILE = NI * 1024;
@@ -380,14 +382,16 @@ constexpr int FR_THREADS = 256;
 
 __global__ __launch_bounds__(FR_THREADS) void fused_em_rows_kernel(
     const float *__restrict__ logits, const int64_t *__restrict__ labels, float *__restrict__ loss_rows,
-    float *__restrict__ pi, int64_t B, int C, float inv_scale, float tol, int K,
-    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters, void *ws,
+    float *__restrict__ pi, void *ws, int64_t B, int C, int Ls, int K, float inv_scale, float tol,
+    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters,
     unsigned long long *__restrict__ dbg, int G, int verify) {
+    // (argument order = order of first use, the first 56 bytes preloaded, as fused_em_kernel; Ls: the rows of a
+    //  workgroup, ceil(B / G), from the launcher -- no 64-bit division in front of the first load)
     __shared__ TbShared<FR_THREADS / WAVE, tb_stage(1, FR_THREADS)> sh;
     const int tid = threadIdx.x;
     const int b = (int)blockIdx.x;
     WsHeader *hdr = reinterpret_cast<WsHeader *>(ws);
-    const int64_t L = (B + G - 1) / G;
+    const int64_t L = Ls;
     const int64_t lo = (int64_t)b * L < B ? (int64_t)b * L : B;
     const int64_t hi = lo + L < B ? lo + L : B;
     const int64_t row = lo + tid;
@@ -457,16 +461,18 @@ __global__ __launch_bounds__(FR_THREADS) void fused_em_rows_kernel(
 template <int KMAX>
 __global__ __launch_bounds__(FR_THREADS) void fused_em_rows4_kernel(
     const float *__restrict__ logits, const int64_t *__restrict__ labels, float *__restrict__ loss_rows,
-    float *__restrict__ pi, int64_t B, int C, float inv_scale, float tol, int K,
-    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters, void *ws,
+    float *__restrict__ pi, void *ws, int64_t B, int C, int Ls, int K, float inv_scale, float tol,
+    float *__restrict__ grad, float *__restrict__ out, int32_t *__restrict__ out_iters,
     unsigned long long *__restrict__ dbg, int G, int verify) {
+    // (argument order = order of first use, the first 56 bytes preloaded, as fused_em_kernel; Ls: the rows of a
+    //  workgroup, ceil(B / G), from the launcher -- no 64-bit division in front of the first load)
     constexpr int V = 4, LG = 4;
     __shared__ TbShared<FR_THREADS / WAVE, tb_stage(1, FR_THREADS)> sh;
     const int tid = threadIdx.x;
     const int g = tid & (LG - 1);
     const int b = (int)blockIdx.x;
     WsHeader *hdr = reinterpret_cast<WsHeader *>(ws);
-    const int64_t L = (B + G - 1) / G;                               // rows of a workgroup (<= ROWS: the launcher)
+    const int64_t L = Ls;                                            // rows of a workgroup (<= ROWS: the launcher)
     const int64_t row = (int64_t)b * L + (tid >> 2);
     const bool have = (tid >> 2) < L && row < B;
     const int nv = C / V;
@@ -557,11 +563,12 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         auto kern = fused_em_rows_kernel;
         int G = coop_cap(kern, FR_THREADS);
         if (G > TB_G) G = TB_G;
-        if (G >= TJ_MAXK && (B + G - 1) / G <= FR_THREADS) {
+        const int64_t L = G > 0 ? (B + G - 1) / G : 0;      // rows of a workgroup
+        if (G >= TJ_MAXK && L <= FR_THREADS) {
             const int debug = tune_get("RLVI_TJ_DEBUG", 0);
             unsigned long long *dbg = debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
-            *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, B, (int)C,
-                         inv_scale, tol, maxiter, grad, out, out_iters, ws, dbg, G, tune_get("RLVI_TJ_VERIFY", 0));
+            *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, ws, B, (int)C,
+                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, tune_get("RLVI_TJ_VERIFY", 0));
             return 1;
         }
         return 0;
@@ -577,9 +584,10 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         auto go = [&](auto kern) {
             int G = coop_cap(kern, FR_THREADS);
             if (G > TB_G) G = TB_G;
-            if (G < TJ_MAXK || (B + G - 1) / G > FR_THREADS / 4) return 0;   // node k is reduced by workgroup k; 64 rows each
-            *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, B, (int)C,
-                         inv_scale, tol, maxiter, grad, out, out_iters, ws, dbg, G, verify);
+            const int64_t L = G > 0 ? (B + G - 1) / G : 0;
+            if (G < TJ_MAXK || L > FR_THREADS / 4) return 0;   // node k is reduced by workgroup k; 64 rows each
+            *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, ws, B, (int)C,
+                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, verify);
             return 1;
         };
         if (C <= 64 ? go(fused_em_rows4_kernel<4>) : go(fused_em_rows4_kernel<8>)) return 1;
@@ -603,8 +611,8 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         const size_t lds = (size_t)FE_WAVES * FE_TPW * (K_) * 1024;                                  \
         if (allow_dyn_lds(kern, lds) != 0) break;                                                    \
         if (coop_cap(kern, FE_THREADS, lds) < G) break;     /* all G workgroups must be resident */  \
-        *rc = launch(kern, dim3((unsigned)G), dim3(FE_THREADS), lds, st, logits, labels, loss_rows, pi, B, \
-                     (int)C, inv_scale, tol, maxiter, grad, out, out_iters, ws, dbg, G, verify);     \
+        *rc = launch(kern, dim3((unsigned)G), dim3(FE_THREADS), lds, st, logits, labels, loss_rows, pi, ws, B, \
+                     (int)C, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, verify);         \
         launched = 1;                                                                                \
     } while (0)
     if (k <= 4) RLVI_FE(4, false);

@@ -51,10 +51,12 @@ __device__ __forceinline__ void write_partial(double *part, double ta, double th
 template <typename T, int V, int G, int KMAX>
 __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
     const T *__restrict__ logits, int64_t ld, const int64_t *__restrict__ labels,
-    const int64_t *__restrict__ idx, const float *__restrict__ weights,
-    float *__restrict__ residuals, int64_t N, int64_t B, int C, int kact, float inv_scale,
+    const int64_t *__restrict__ idx, int64_t B, int C, int kact, const float *__restrict__ weights,
+    int64_t N, float *__restrict__ residuals, float inv_scale,
     const float *__restrict__ grad_scale, T *__restrict__ grad, int64_t ldg, double *__restrict__ part,
     int32_t *__restrict__ status, int accum, double inv_rows100, int64_t first_row) {
+    // (argument order = order of first use: what the first row loads need lies in the first 56 bytes, which arrive in
+    //  SGPRs at wave start -- rlvi_amd/_build.py: kernarg preload; the same in the other forms below)
     constexpr int R = WAVE / G;  // rows per wave
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
@@ -200,8 +202,8 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
 template <typename T, int V, int WPR>
 __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
     const T *__restrict__ logits, int64_t ld, const int64_t *__restrict__ labels,
-    const int64_t *__restrict__ idx, const float *__restrict__ weights,
-    float *__restrict__ residuals, int64_t N, int64_t B, int C, float inv_scale,
+    const int64_t *__restrict__ idx, int64_t B, int C, int64_t N, const float *__restrict__ weights,
+    float *__restrict__ residuals, float inv_scale,
     const float *__restrict__ grad_scale, T *__restrict__ grad, int64_t ldg, double *__restrict__ part,
     int32_t *__restrict__ status, int accum, double inv_rows100) {
     constexpr int U = 4;                                          // vectors per lane and trip
@@ -358,6 +360,8 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
 // ---------------------------------------------------------------------------------------
 // -DRLVI_MSTEP_STAMPS: diagnostic build, every wave leaves wall-clock stamps (100 MHz) of its first
 // tile's phases in the workspace scratch (tools/mstep_stamps.py); never in the product library.
+// Stamp 0 is the wall clock as the kernel's very first instruction (it needs no argument) and stamp 1 the issue of
+// the first tile's loads; both wait in registers until the stamp pointer, which hangs on an argument, is there.
 #ifdef RLVI_MSTEP_STAMPS
 #define RLVI_STAMP(k) do { if (lane == 0 && first_tile) stamps[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -374,10 +378,39 @@ struct FMaxF { __device__ __forceinline__ float operator()(float a, float b) con
 template <typename T, int V, int G, int KMAX, int WPB, bool EXACT>
 __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_kernel(
     const T *__restrict__ logits, const int64_t *__restrict__ labels,
-    const int64_t *__restrict__ idx, const float *__restrict__ weights,
-    float *__restrict__ residuals, int64_t N, int64_t nfull, int C, float inv_scale,
+    const int64_t *__restrict__ idx, int64_t nfull, int C, int hold_ticks, const float *__restrict__ weights,
+    int64_t N, float *__restrict__ residuals, float inv_scale,
     const float *__restrict__ grad_scale, T *__restrict__ grad, double *__restrict__ part,
-    int32_t *__restrict__ status, int accum, double inv_rows100, int hold_ticks, int gen_ticks) {
+    int32_t *__restrict__ status, int accum, double inv_rows100, int gen_ticks) {
+    // Argument order = order of first use.  logits ... N are the first 56 bytes, preloaded into SGPRs at wave start:
+    // the tile grid, the hold's clock and the addresses of the label, index and tile loads need nothing else, so
+    // those loads leave without a wait for the argument block; the rest is waited for once, behind them.
+#ifdef RLVI_MSTEP_STAMPS
+    // The compiler puts its own fetch of the arguments past the preloaded ones at the top of the kernel, in front
+    // of anything written here.  So this build does not touch those parameters: it reads them (and the grid size,
+    // which the runtime appends to them) from the argument block itself, through a pointer that exists only behind
+    // the stamp (offsets = the signature's layout).
+    unsigned long long t_entry;
+    typedef const __attribute__((address_space(4))) char *ms_ka_t;
+    ms_ka_t ka = (ms_ka_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("s_memrealtime %0" : "=s"(t_entry));
+    asm volatile("" : "+s"(ka));
+    __builtin_amdgcn_sched_barrier(0);
+#define MS_LATE(U, off) (*(U const __attribute__((address_space(4))) *)(ka + (off)))
+    residuals = MS_LATE(float *, 56);
+    inv_scale = MS_LATE(float, 64);
+    grad_scale = MS_LATE(const float *, 72);
+    grad = MS_LATE(T *, 80);
+    part = MS_LATE(double *, 88);
+    status = MS_LATE(int32_t *, 96);
+    accum = MS_LATE(int, 104);
+    inv_rows100 = MS_LATE(double, 112);
+    gen_ticks = MS_LATE(int, 120);
+    const unsigned grid_x = MS_LATE(unsigned, 128);
+#undef MS_LATE
+#else
+    const unsigned grid_x = gridDim.x;
+#endif
     constexpr int R = WAVE / G;                                   // rows per wave tile
     constexpr int VB = V * (int)sizeof(T);                        // bytes of a lane vector
     constexpr int NI = (KMAX * VB + 15) / 16;                     // 1-KiB pieces per tile (max)
@@ -392,16 +425,9 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     const int nchunk = (R * C * (int)sizeof(T)) >> 4;            // 16-byte chunks of a tile
     char *wtile = smem + (size_t)wave * WTILE;
     vu4 *tile16 = reinterpret_cast<vu4 *>(wtile);
-    const int64_t tstride = (int64_t)gridDim.x * WPB;
+    unsigned ngrid = grid_x;
 #ifdef RLVI_MSTEP_STAMPS
-    unsigned long long *stamps = reinterpret_cast<unsigned long long *>(
-        reinterpret_cast<char *>(status) + WS_SCRATCH_OFF) + ((size_t)blockIdx.x * WPB + wave) * 16;
     bool first_tile = true;
-    RLVI_STAMP(0);
-    if (lane == 0) {
-        stamps[8] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));     // HW_REG_HW_ID
-        stamps[9] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));    // HW_REG_XCC_ID
-    }
 #endif
 
     // loop-invariant per-lane geometry
@@ -423,7 +449,16 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     const int row_off = sub * C * (int)sizeof(T);
     const int64_t *idxp = idx != nullptr ? idx : labels;
     const unsigned sub8 = (unsigned)sub * 8u;
-    const float gscale = grad_gain(inv_scale, grad_scale);
+    // ENTRY_FIRST (the 16-wave fp32 form, one tile per wave: the launch is as long as a wave's own latency): nothing
+    // that hangs on an argument past the preloaded ones is touched in front of the first tile's loads.  The
+    // gradient's gain (later arguments and, under a GradScaler, a load) is taken behind their issue, and the later
+    // arguments pass through an empty asm inside the loop so that nothing derived from them is hoisted in front of
+    // it.  The other forms keep the gain and the loop invariants in front of the loop: they stride over several
+    // tiles or sit at a register bound, where carrying these through the loop costs a register, i.e. a wave per
+    // SIMD or a spill.
+    constexpr bool ENTRY_FIRST = WPB == 16 && sizeof(T) == 4;
+    float gscale = ENTRY_FIRST ? 0.0f : grad_gain(inv_scale, grad_scale);
+    bool have_gain = !ENTRY_FIRST;
 
     float acc = 0.0f, hits = 0.0f;
     bool bad = false;
@@ -447,8 +482,8 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
     // (The launcher takes this form only when no wave has a second tile and the grid fills at least four
     //  fifths of the CUs; a wave without a tile only joins the barrier.)
     constexpr bool CUWIDE = WPB == 16;
-    if (CUWIDE && (int64_t)blockIdx.x * WPB + wave >= nfull) __syncthreads();
-    for (int64_t t = (int64_t)blockIdx.x * WPB + wave; t < nfull; t += tstride) {
+    if (!ENTRY_FIRST && CUWIDE && (int64_t)blockIdx.x * WPB + wave >= nfull) __syncthreads();
+    for (int64_t t = (int64_t)blockIdx.x * WPB + wave; t < nfull; t += (int64_t)ngrid * WPB) {
         const int64_t row_base = t * R;
         // ---- A
         const char *src = reinterpret_cast<const char *>(logits + row_base * C);
@@ -460,11 +495,32 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
 #pragma unroll
         for (int i = 0; i < NI; ++i)
             stg[i] = __builtin_nontemporal_load(reinterpret_cast<const vu4 *>(src + dma_off[i]));
-        RLVI_STAMP(1);
+#ifdef RLVI_MSTEP_STAMPS
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_sched_barrier(0);
+        unsigned long long *stamps = reinterpret_cast<unsigned long long *>(
+            reinterpret_cast<char *>(status) + WS_SCRATCH_OFF) + ((size_t)blockIdx.x * WPB + wave) * 16;
+        if (lane == 0 && first_tile) {
+            stamps[0] = t_entry;
+            stamps[1] = t_issued;
+            stamps[8] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));     // HW_REG_HW_ID
+            stamps[9] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));    // HW_REG_XCC_ID
+        }
+#endif
+        // ENTRY_FIRST: the arguments past the preloaded ones that the loop uses (and the grid size, which the runtime
+        // appends to them) pass through here: the compiler asks for them in one burst and waits once, at this
+        // point of the program.  (No instruction.)
+        if constexpr (ENTRY_FIRST)
+            asm volatile("" : "+s"(residuals), "+s"(inv_scale), "+s"(grad_scale), "+s"(grad), "+s"(gen_ticks), "+s"(ngrid));
         if (CUWIDE) {
             __builtin_amdgcn_sched_barrier(0);       // (the loads are issued, THEN the barrier)
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if (ENTRY_FIRST && !have_gain) {             // (wave-uniform; behind the barrier)
+            gscale = grad_gain(inv_scale, grad_scale);
+            have_gain = true;
         }
         bool okrow = true;
         ix = idx != nullptr ? ix : row_base + sub;
@@ -601,6 +657,9 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
 #endif
     }
 
+    // (ENTRY_FIRST: a wave without a tile joins the barrier of its workgroup's one generation of tiles here, behind
+    //  the loop it did not enter, so that its wait for the barrier is not the first thing in the kernel)
+    if (ENTRY_FIRST && (int64_t)blockIdx.x * WPB + wave >= nfull) __syncthreads();
     // every lane of a row's group carried the row's sums: count each row once
     double a = wave_sum((double)(g == 0 ? acc : 0.0f));
     double h = wave_sum((double)(g == 0 ? hits : 0.0f));
@@ -630,7 +689,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
 template <typename T, int KW, int WPB>
 __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
     const T *__restrict__ logits, const int64_t *__restrict__ labels, const int64_t *__restrict__ idx,
-    const float *__restrict__ weights, float *__restrict__ residuals, int64_t N, int64_t nfull, int C,
+    int64_t nfull, int C, const float *__restrict__ weights, int64_t N, float *__restrict__ residuals,
     float inv_scale, const float *__restrict__ grad_scale, T *__restrict__ grad, double *__restrict__ part,
     int32_t *__restrict__ status, int accum, double inv_rows100) {
     static_assert(sizeof(T) == 2, "word-wise tile of 2-byte elements");
@@ -841,8 +900,8 @@ struct MstepCall {
     int rows(int64_t first, int64_t nb) const {
         const int kact = ((C + V - 1) / V + G - 1) / G;
         return launch(mstep_kernel<T, V, G, KMAX>, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, st,
-                      logits + first * ld, ld, labels + first, idx != nullptr ? idx + first : idx, weights,
-                      residuals, N, B - first, C, kact, inv_scale, grad_scale,
+                      logits + first * ld, ld, labels + first, idx != nullptr ? idx + first : idx, B - first, C, kact,
+                      weights, N, residuals, inv_scale, grad_scale,
                       grad != nullptr ? grad + first * ldg : grad, ldg, part, status, first > 0 ? 1 : accum,
                       inv_rows100, first);
     }
@@ -868,9 +927,9 @@ static int launch_wave(const MstepCall<T> &c, bool exact, int64_t nb, int64_t nf
         if constexpr (WPB == 16) {      // (> 64 KiB of dynamic LDS)
             if (const int e = allow_dyn_lds(kern, LDS)) return e;
         }
-        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), LDS, c.st, c.logits, c.labels, c.idx, c.weights,
-                      c.residuals, c.N, nfull, c.C, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,
-                      c.inv_rows100, hold_ticks, gen_ticks);
+        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), LDS, c.st, c.logits, c.labels, c.idx, nfull, c.C,
+                      hold_ticks, c.weights, c.N, c.residuals, c.inv_scale, c.grad_scale, c.grad, c.part, c.status,
+                      c.accum, c.inv_rows100, gen_ticks);
     };
     return exact ? go(mstep_wave_kernel<T, V, G, KMAX, WPB, true>) : go(mstep_wave_kernel<T, V, G, KMAX, WPB, false>);
 }
@@ -1027,7 +1086,7 @@ static int dispatch_gk(const MstepCall<T> &c) {
         ws_note_mstep(c.ws, 5);
         auto go = [&](auto kern) {
             return launch(kern, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, c.st, c.logits, c.ld, c.labels, c.idx,
-                          c.weights, c.residuals, c.N, B, C, c.inv_scale, c.grad_scale, c.grad, c.ldg, c.part, c.status,
+                          B, C, c.N, c.weights, c.residuals, c.inv_scale, c.grad_scale, c.grad, c.ldg, c.part, c.status,
                           c.accum, c.inv_rows100);
         };
         return c.finish(wide ? go(mstep_longrow_kernel<T, V, MSTEP_WAVES>) : go(mstep_longrow_kernel<T, V, 1>), nb);
@@ -1063,8 +1122,8 @@ static int launch_bf16w(const MstepCall<T> &c) {
     const int kw = ((c.C + 3) / 4 + 1) / 2;        // words of a lane's segment of ceil(C / 4) elements
     ws_note_mstep(c.ws, 4);
     auto go = [&](auto kern) {
-        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), lds, c.st, c.logits, c.labels, c.idx, c.weights,
-                      c.residuals, c.N, nfull, c.C, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,
+        return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), lds, c.st, c.logits, c.labels, c.idx, nfull, c.C,
+                      c.weights, c.N, c.residuals, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,
                       c.inv_rows100);
     };
     const int rc = kw <= 8    ? go(mstep_bf16w_kernel<T, 8, WPB>)

@@ -124,25 +124,78 @@ __device__ __forceinline__ void store_rec(gu64 *p, uint32_t tag, int nq, const f
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// warm-start state of the previous call (read it ahead of the slice loads: its latency hides there)
+// warm-start state of the previous call
 struct TbWarm {
     bool warm;
     float shift;      // guess of min(l); NLLs are >= 0
-    float rn_l;       // lane k: guessed node k
+    float node;       // lane k: node k of the last call as loaded; in the fat forms already the guess made of it
     int it;
 };
-__device__ __forceinline__ TbWarm tb_warm(void *ws, int64_t N, int K, bool sharded = false, bool cold = false) {
+// The state as loaded.  Three steps:
+//   tb_warm_issue   right behind the issue of the slice loads.  Five unconditional, independent loads: they all
+//                   leave before anything waits, and their round trip to the workspace runs beside the slice's.
+//   tb_warm_pin     where the scalar ones are waited for, once.  (estep_trajb_kernel spells the pin out itself: it
+//                   waits for its arguments past the preloaded ones in the same place.)
+//   tb_warm_select  the selects, behind the loads: warm, shift, it, the nodes.
+struct TbWarmRaw {
+    long long n;
+    int k, it;
+    float shift, node;
+};
+__device__ __forceinline__ TbWarmRaw tb_warm_issue(void *ws, bool sharded) {
     const TrajState *state = reinterpret_cast<const TrajState *>(static_cast<char *>(ws) +
                                                                  (sharded ? WS_PEER_STATE_OFF : WS_TRAJ_OFF));
+    static_assert(WAVE <= TJ_MAXK, "every lane has a node slot to read");
+    // (wave-uniform, and told so: the pin takes SGPRs whichever kind of load the compiler picks -- behind a store
+    //  or a clock read, as in the lab builds with stamps, it does not take scalar ones)
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    const long long n = state->n;
+    TbWarmRaw r;
+    r.n = (long long)(((unsigned long long)(unsigned)uni((int)(n >> 32)) << 32) | (unsigned)uni((int)n));
+    r.k = uni(state->k);
+    r.shift = __int_as_float(uni(__float_as_int(state->shift)));
+    r.it = uni(state->it);
+    r.node = state->nodes[threadIdx.x & (WAVE - 1)];
+    return r;
+}
+__device__ __forceinline__ void tb_warm_pin(TbWarmRaw &r) {
+    asm volatile("" : "+s"(r.n), "+s"(r.k), "+s"(r.it), "+s"(r.shift));
+}
+// lane k: guessed node k
+__device__ __forceinline__ float tb_warm_guess(bool warm, float node, int K) {
     const int lane = threadIdx.x & (WAVE - 1);
+    float rn_l = lane < K ? (warm ? node : 19.0f * exp2f(-(float)lane)) : 1.0f;
+    if (lane == 0) rn_l = (float)(0.95 / (1.0 - 0.95));
+    return rn_l;
+}
+// EARLY_NODES: make the guessed nodes here and not inside the solve.  The thin forms leave the state's one vector
+// load untouched until the solve has issued its own first loads (a wait for it in front of them would put their
+// round trip behind the slice's); the fat forms have no register to carry it that far (16 x 512 is at its 256).
+template <bool EARLY_NODES = false>
+__device__ __forceinline__ TbWarm tb_warm_select(const TbWarmRaw &r, int64_t N, int K, bool cold) {
     TbWarm w;
-    w.warm = !cold && state->n == (long long)N && state->k == K;
-    w.shift = w.warm ? state->shift : 0.0f;
-    w.rn_l = lane < K ? (w.warm ? state->nodes[lane] : 19.0f * exp2f(-(float)lane)) : 1.0f;
-    if (lane == 0) w.rn_l = (float)(0.95 / (1.0 - 0.95));
-    w.it = w.warm ? state->it : 0;
+    w.warm = !cold && r.n == (long long)N && r.k == K;
+    w.shift = w.warm ? r.shift : 0.0f;
+    w.node = r.node;
+    if (EARLY_NODES) {
+        const int lane = threadIdx.x & (WAVE - 1);
+        float rn = lane < K ? (w.warm ? r.node : 19.0f * exp2f(-(float)lane)) : 1.0f;
+        if (lane == 0) rn = (float)(0.95 / (1.0 - 0.95));
+        w.node = rn;
+    }
+    w.it = w.warm ? r.it : 0;
     return w;
 }
+constexpr bool tb_early_nodes(int E, int block) { return !tb_nsplit(E, block); }
+// (callers whose arguments need no pinning: the in-batch kernels)
+__device__ __forceinline__ TbWarm tb_warm(void *ws, int64_t N, int K) {
+    TbWarmRaw r = tb_warm_issue(ws, false);
+    tb_warm_pin(r);
+    return tb_warm_select(r, N, K, false);
+}
+
+// flags of estep_trajb_kernel (one preloaded argument)
+enum { TBF_VERIFY = 1, TBF_COLD = 2, TBF_SHARDED = 4 };
 
 struct TbSolved {
     float r_fin;      // eps/(1-eps) at the accepted fixed point
@@ -207,9 +260,9 @@ __device__ __forceinline__ TbSolved trajb_solve(
     const int wave = tid / WAVE;
     const int swave = wave % (TB_BLOCK / WAVE);      // wave inside its sampling group
     const int sgrp = wave / (TB_BLOCK / WAVE);       // sampling group
-    // ---- warm-start state (the caller read it ahead of its slice loads)
+    // ---- warm-start state (the caller issued its loads: tb_warm_issue)
     const float shift = wm.shift;
-    float rn_l = wm.rn_l;
+    float rn_l = tb_early_nodes(E, TB_BLOCK) ? wm.node : tb_warm_guess(wm.warm, wm.node, K);
     auto round8 = [K](int v) { v = (v + TB_CHUNK - 1) / TB_CHUNK * TB_CHUNK; return v < K ? v : K; };
     int Ke = __builtin_amdgcn_readfirstlane(wm.warm ? round8(wm.it + 2) : K);            // evaluated nodes (uniform)
 

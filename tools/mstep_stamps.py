@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase timeline of the wave-tile M-step kernel from a -DRLVI_MSTEP_STAMPS build.
     RLVI_LIB_PATH=rlvi_amd/librlvi_stamps.so python tools/mstep_stamps.py [--tune NAME=V ...]
-Stamps per wave (first tile): 0 start, 1 DMA issued, 2 tile landed, 3 row max, 4 row sum,
+Stamps per wave (first tile): 0 start (the kernel's first instruction), 1 DMA issued, 2 tile landed, 3 row max, 4 row sum,
 5 arithmetic done, 6 stores issued, 7 stores retired.  Prints percentiles in us since the first wave's start."""
 import argparse
 import os
@@ -44,6 +44,12 @@ for k, nm in enumerate(names):
     print(f"  {nm:15s} {x.min():6.2f} {np.percentile(x, 10):6.2f} {np.median(x):6.2f} {np.percentile(x, 90):6.2f} {x.max():6.2f}")
 d = np.diff(raw[:, :8], axis=1) / 100.0
 print("phase durations (median / p90): " + ", ".join(f"{names[k+1]} {np.median(d[:, k]):.2f}/{np.percentile(d[:, k], 90):.2f}" for k in range(7)))
+
+# (stamp 0 is the kernel's first instruction, stamp 1 the issue of the first tile's loads: what a wave does in
+#  front of its first request for data)
+e2i = (raw[:, 1] - raw[:, 0]) / 100.0
+print(f"entry -> first data load issued, per wave: min {e2i.min():.2f} median {np.median(e2i):.2f} p90 {np.percentile(e2i, 90):.2f} "
+      f"max {e2i.max():.2f} us; the 256 earliest waves: median {np.median(e2i[np.argsort(raw[:, 0])[:256]]):.2f} us")
 
 # placement: HW_ID bits: wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (gfx9 layout); XCC_ID bits 3:0
 hw, xcc = raw[:, 8], raw[:, 9] & 0xF

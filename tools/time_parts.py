@@ -175,6 +175,19 @@ with torch.cuda.stream(side):
             hs = full[996:999].astype(np.int64)
             print("   helper wave [start, done] and the recurrence wave past its second barrier, us on the same axis:",
                   [round(float(v - cs[0]) / 100.0, 2) for v in hs])
+        # the kernel's entry on the stamps' axis: stamped as its first instruction (986 entry, 987 first data loads
+        # issued, 988 slice landed); a build without these has the kernel's length from its entry (961), taken at the
+        # last stamp, and its first two stamps sit behind the issue of the slice loads and behind their arrival
+        if int(full[986]) > 0:
+            e = [int(full[986 + k]) for k in range(3)]
+            print(f"kernel entry at {(e[0] - int(st[0])) / 100.0:.2f}, first data loads issued at {(e[1] - int(st[0])) / 100.0:.2f}, "
+                  f"slice landed at {(e[2] - int(st[0])) / 100.0:.2f} us on the stamps' axis: entry -> issued "
+                  f"{(e[1] - e[0]) / 100.0:.2f} us, entry -> slice landed {(e[2] - e[0]) / 100.0:.2f} us")
+        elif int(full[961]) > 0 and n > 1:
+            e0 = int(st[n - 1]) - int(full[961])
+            print(f"kernel entry (last stamp - kernel length) at {(e0 - int(st[0])) / 100.0:.2f} us on the stamps' axis: entry -> first "
+                  f"stamp (behind the issue of the slice loads) {(int(st[0]) - e0) / 100.0:.2f} us, entry -> slice landed "
+                  f"(second stamp) {(int(st[1]) - e0) / 100.0:.2f} us")
         if int(full[980]) > 0:
             print("sums of workgroup 0 / wave 0: arithmetic done at", round(float(int(full[980]) - int(st[0])) / 100.0, 2),
                   "butterflies done at", round(float(int(full[981]) - int(st[0])) / 100.0, 2), "us since kernel start")
