@@ -321,6 +321,45 @@ int rlvi_jocor_bwd_f16(const uint16_t *logits1, int64_t ld1, const uint16_t *log
                        uint16_t *grad2, int64_t ldg2, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * BARE's batch-statistics pruning, forward.  Replaces WeightedCCE.forward of deep-learning/methods/train_bare.py:28-57
+ * -- softmax and clamp (:33-34), the one-hot block and pt_i = p[i, y_i] (:31-35), torch.mean / torch.std down the
+ * batch (:38-41), the two matmuls against the one-hot block (:42-43), where / index_select / argmax (:44-51), the
+ * second F.cross_entropy (:52-55) -- and the len(prun_idx) host sync (:50); and, through out[3], the top-1 of
+ * accuracy(logits, labels) that train_bare takes beside it (:72).
+ *     p = clamp(softmax(z), 1e-8, 1 - 1e-8);  mu_c = mean_i p[i, c];  sd_c = unbiased deviation of p[:, c] (B - 1)
+ *     row i is kept when  p[i, y_i] - mu[y_i] >= k * sd[y_i]          (fp32, the reference's rounding order)
+ *     L = mean over the kept rows of CE(z_i, y_i); no row kept (always for B = 1, where sd is NaN): the fallback,
+ *     L = mean over all rows.
+ *   logits  [B, C] row-major, leading dimension ld (elements); fp32, bf16 or fp16 (16-bit patterns), arithmetic in
+ *           fp32 on the exactly widened values
+ *   labels  [B] int64; a label outside [0, C) sets RLVI_ST_RANGE, its row is never kept and adds nothing to L
+ *   k       BARE's k (train_bare uses 1); NaN is RLVI_E_SHAPE
+ *   w    [B] fp32 out: 1 / n_kept on the kept rows, else 0; 1 / B on every row in the fallback
+ *   sel  [B] fp32 out: 1.0 on the kept rows, else 0.0; all ones in the fallback
+ *   out  [4] fp32 out: { L, n_kept (B in the fallback), fallback (0 / 1), 100 * top-1 hits / B }
+ *   grad [B, C] (ldg) in the logits' dtype or NULL: written by the one-workgroup form only (see below)
+ *   ws   a workspace of any size (the slabs of the column sums take its weighted-least-squares region)
+ * No gradient flows through the statistics: dL/dz_i = w_i (softmax(z_i) - e_y).  Two forms (rlvi_bare_form tells
+ * which one a shape takes: 1 / 0, or RLVI_E_SHAPE / RLVI_E_LIMIT; knob RLVI_BARE_FORM: -1 by size, 0 streaming,
+ * 1 one workgroup wherever the block fits it):
+ *   one workgroup, B * C <= 16 384 with B <= 1024 and C <= 1024 (the reference's batches, 32 x 10 to 128 x 100):
+ *       statistics, selection, L and -- if grad != NULL -- the gradient w_i (softmax - e_y), rounded once, in ONE launch;
+ *   streaming, everything else: two launches (pass 1 over the block, then one finishing workgroup), no host round
+ *       trip; `grad` is left alone: the gradient is rlvi_mstep_fwd_bwd_* with weights = w, idx = NULL, inv_scale = 1
+ *       (an upstream gradient or a loss scale goes in as its grad_scale, or multiplies the B values of w).
+ * Both forms give the same sel, bit for bit, and every run gives the same bits: the column sums are exact fixed-point
+ * integers (p, p^2 in units of 2^-40), the deviation is taken from them without a rounded subtraction.
+ * C <= 4096 and B <= 2^22 (RLVI_E_LIMIT beyond).  Rows may be strided.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_bare_form(int64_t B, int64_t C);
+int rlvi_bare_fwd_f32(const float *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C, float k, float *w,
+                      float *sel, float *out, float *grad, int64_t ldg, void *ws, void *stream);
+int rlvi_bare_fwd_bf16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C, float k,
+                       float *w, float *sel, float *out, uint16_t *grad, int64_t ldg, void *ws, void *stream);
+int rlvi_bare_fwd_f16(const uint16_t *logits, int64_t ld, const int64_t *labels, int64_t B, int64_t C, float k,
+                      float *w, float *sel, float *out, uint16_t *grad, int64_t ldg, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * CDR's gradient masking over all weight tensors of a network.  Replaces deep-learning/methods/train_cdr.py:22-44:
  * the torch.cat of every covered gradient and parameter (:22-29), metric = |g * v| (:30), torch.topk(metric, nz)
  * read for its last value (:33-34) and, per tensor, mask = (|v * g| >= thresh) * clip; g = mask * g (:40-44) --

@@ -69,6 +69,10 @@ SIGNATURES = {
                                    _vp, _i64, _vp, _i64, _vp]),
     "rlvi_jocor_bwd_f16": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp,
                                   _vp, _i64, _vp, _i64, _vp]),
+    "rlvi_bare_form": (_int, [_i64, _i64]),
+    "rlvi_bare_fwd_f32": (_int, [_vp, _i64, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rlvi_bare_fwd_bf16": (_int, [_vp, _i64, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rlvi_bare_fwd_f16": (_int, [_vp, _i64, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "rlvi_cdr_table_bytes": (ctypes.c_size_t, [_int]),
     "rlvi_cdr_table_fill": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64), _int,
                                    ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),

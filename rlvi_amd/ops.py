@@ -769,6 +769,93 @@ def jocor_loss(logits1, logits2, labels, forget_rate, co_lambda=0.1, ws=None, ou
     return loss
 
 
+def _bare_call(logits, labels, k, out, ws, want_grad):
+    """The dtype's BARE entry on checked inputs: (out, w, sel, grad).  grad is the gradient of L in the logits' dtype
+    when the shape takes the one-workgroup form (which writes it in the same launch) and want_grad is set, else
+    None: the streaming form leaves the gradient to the M-step entry (_BareLoss.backward)."""
+    L = _lib.load()
+    B, C = logits.shape
+    dev = logits.device
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    w = torch.empty(B, dtype=torch.float32, device=dev)
+    sel = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = ws or workspace(dev)
+    form = L.rlvi_bare_form(B, C)
+    _lib.check(min(form, 0), "rlvi_bare_form")
+    grad = torch.empty((B, C), dtype=logits.dtype, device=dev) if (want_grad and form == 1) else None
+    fn = _entry(L, "bare_fwd", logits.dtype)
+    _lib.check(fn(_ptr(logits), logits.stride(0), _ptr(labels), B, C, float(k), _ptr(w), _ptr(sel), _ptr(out),
+                  _ptr(grad), C if grad is not None else 0, ws.ptr, _stream_ptr()), "rlvi_bare_fwd")
+    return out, w, sel, grad
+
+
+def _bare_inputs(logits, labels):
+    _require_gpu(logits, labels)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, C]")
+    if labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError("labels must be a [B] vector")
+    return _as_logits(logits), _as_int64(labels)
+
+
+def bare_forward(logits, labels, k=1.0, out=None, ws=None):
+    """Forward of BARE's WeightedCCE (train_bare.py:28-57) without autograd.  Returns (out, w, sel): out fp32[4] =
+    {L, n_kept, fallback, top-1 %}, w [B] = 1 / n_kept on the kept rows and 0 elsewhere (1 / B everywhere in the
+    fallback), sel [B] the 0/1 selection -- all on the device, no host synchronisation.  See include/rlvi_hip.h."""
+    logits, labels = _bare_inputs(logits, labels)
+    out, w, sel, _ = _bare_call(logits, labels, k, out, ws, False)
+    return out, w, sel
+
+
+class _BareLoss(torch.autograd.Function):
+    """L = mean CE of the rows BARE keeps.  The one-workgroup form has written the gradient in the forward launch and
+    backward hands it out (as _WeightedCE does); otherwise backward is the streaming M-step entry with weights = w,
+    idx = None, inv_scale = 1 (as _SelectedCE), the upstream gradient staying on the device: it multiplies the B
+    values of w (fp32 / bf16) or goes in as the kernel's grad_scale (fp16: one rounding of the scaled gradient)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, k, ws, out):
+        z = logits.detach()
+        out, w, sel, grad = _bare_call(z, labels, k, out, ws, ctx.needs_input_grad[0])
+        ctx.fused = grad is not None
+        ctx.ws = ws
+        if ctx.fused:
+            ctx.save_for_backward(grad)
+        else:
+            ctx.save_for_backward(z, labels, w)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.detach().to(torch.float32)
+        if ctx.fused:
+            (grad,) = ctx.saved_tensors
+            return grad * g.to(grad.dtype), None, None, None, None
+        z, labels, w = ctx.saved_tensors
+        if z.dtype == torch.float16:
+            _, grad = mstep_fwd_bwd(z, labels, None, w, None, inv_scale=1.0, grad_scale=g.reshape(1), ws=ctx.ws)
+        else:
+            _, grad = mstep_fwd_bwd(z, labels, None, w * g, None, inv_scale=1.0, ws=ctx.ws)
+        return grad, None, None, None, None
+
+
+def bare_loss(logits, labels, k=1.0, ws=None, out=None, check=True):
+    """WeightedCCE.forward of deep-learning/methods/train_bare.py:28-57 on the device: a 0-dim fp32 tensor L, the mean
+    cross-entropy of the rows whose label probability clears its class's batch mean by k batch deviations (of all
+    rows when none does), with the gradient for the logits -- none flows through the statistics.  fp32, bf16 and
+    fp16 logits run natively (any other dtype as fp32); the gradient comes back in the logits' dtype.  Works under
+    torch.autocast and with a GradScaler.  out: optional fp32[4] device tensor that receives {L, n_kept, fallback,
+    top-1 %}.  check=True reads the device status (one 4-byte copy and a sync, as the reference's len(prun_idx) is)
+    and raises on a label out of range; a training loop passes False and reads the status once at its end."""
+    z, labels = _bare_inputs(logits, labels)
+    ws = ws or workspace(z.device)
+    loss = _BareLoss.apply(z, labels, float(k), ws, out)
+    if check:
+        ws.raise_on_status("bare_loss")
+    return loss
+
+
 def cdr_covered(params):
     """The tensors CDR's mask covers (train_cdr.py:25,:41): those with dim() in (2, 4), in the order given."""
     return [p for p in params if p.dim() in (2, 4)]

@@ -225,3 +225,12 @@ def jocor_rate_schedule(forget_rate, n_epoch, num_gradual, exponent=1.0):
     rs = np.ones(n_epoch) * forget_rate
     rs[:num_gradual] = np.linspace(0, forget_rate ** exponent, num_gradual)
     return rs
+
+
+def bare_dense_inputs(B, C, scale, seed):
+    """Inputs of golden set G14's dense cases: logits scale * N(0, 1) [B, C] fp32 and uniform labels [B] int64 --
+    softmax columns of one narrow mode each, so that many rows sit near BARE's mean + k * std boundary."""
+    rng = np.random.default_rng(seed)
+    logits = (scale * rng.standard_normal((B, C))).astype(np.float32)
+    labels = rng.integers(0, C, B).astype(np.int64)
+    return logits, labels
