@@ -116,6 +116,8 @@ size_t rlvi_workspace_region(const char *name, size_t *bytes);
  *   inv_scale   1/B for one device; 1/global_B when the batch is sharded over ranks
  *   grad_logits [B, C] (ldg) or NULL for forward only: inv_scale*pi_i*(softmax - onehot)
  *   out         [4] fp32 device: { sum_i pi_i*l_i * inv_scale, 100*hits/B, sum_i pi_i*l_i, hits }
+ *               (a row with pi_i == 0 adds nothing to the sums, also when l_i is +inf: the small-loss baselines and
+ *                BARE pass their 0/1 selection as the weights)
  * bf16 variant: logits / grad_logits are bfloat16, arithmetic is fp32 on the widened values.
  * Any C up to 2^20 (RLVI_E_LIMIT beyond); rows of more than 512 vectors (C > 2048 fp32 / 4096 bf16 with aligned
  * rows, C > 512 with an odd length or pitch) take a form that reads the row three times (a wave per row, a workgroup

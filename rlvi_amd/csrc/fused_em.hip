@@ -279,7 +279,7 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
         s = group_sum<LG>(s);
         float l = __builtin_amdgcn_logf(s) * 0.69314718055994530942f - (zy - m);
         bool hit = zy == m;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && s >= 2.0f) != 0, 0)) {
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && !(s < 2.0f)) != 0, 0)) {
             // two exact maxima: the label counts only if it is the FIRST column at the maximum
             // (torch.max order, deep-learning/utils.py:58); the tile still holds the logits here
             int earlier = 0;

@@ -45,6 +45,11 @@ __device__ __forceinline__ void write_partial(double *part, double ta, double th
     } else { p[0] = v0; p[1] = v1; p[2] = ta; p[3] = th; }
 }
 
+// A row's term of the batch loss.  A weight of exactly zero takes the row out of the sum whatever its NLL: the
+// small-loss baselines and BARE hand their 0/1 selection in as weights, and a row they drop may well have an NLL of
+// +inf (its label's class masked to -inf), which 0 * inf would turn into a NaN loss over the rows they kept.
+__device__ __forceinline__ float weighted_nll(float li, float pi) { return pi != 0.0f ? li * pi : 0.0f; }
+
 // A row is owned by G consecutive lanes; lane g holds the vectors k*G+g, k < kact <= KMAX, so one
 // load instruction reads G*V contiguous elements of each of the wave's 64/G rows and a lane
 // amortises the (short) lane-group reductions over up to KMAX*V elements.
@@ -156,8 +161,9 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
         // top-1: the label is a hit when it is the FIRST column that attains the row maximum
         // (torch.max order, deep-learning/utils.py:58); two exact maxima put at least 2.0 into the
         // sum, so the exact check (a second read of the row) runs only for waves that hold such a row
+        // (!(s < 2): a row of -inf alone has a NaN sum and every column at its maximum -- it takes the check too)
         bool hit = zy == m;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && s >= 2.0f) != 0, 0)) {
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && !(s < 2.0f)) != 0, 0)) {
             int earlier = 0;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
         }
         if (g == 0 && row_ok) {
             if (residuals != nullptr) residuals[ix] = li;
-            acc += li * pi;
+            acc += weighted_nll(li, pi);
             hits += hit ? 1.0f : 0.0f;
         }
     }
@@ -322,7 +328,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
         const bool hit = zy == m && earlier == 0;
         if (t == 0 && row_ok) {
             if (residuals != nullptr) residuals[ix] = li;
-            acc += li * pi;
+            acc += weighted_nll(li, pi);
             hits += hit ? 1.0f : 0.0f;
         }
         if (WPR > 1) __syncthreads();                             // (shf / shi are rewritten by the next row)
@@ -580,7 +586,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
         // the sum, so the exact check runs only for waves that hold such a row.
         pi = okrow ? pi : 0.0f;                                   // a rejected row gets a zero gradient
         bool hit = zy == m;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && s >= 2.0f) != 0, 0)) {
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit && !(s < 2.0f)) != 0, 0)) {
             int earlier = 0;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
@@ -621,7 +627,7 @@ __global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_ke
             }
         }
         if (g == 0 && okrow && residuals != nullptr) residuals[ix] = li;
-        acc += okrow ? li * pi : 0.0f;
+        acc += okrow ? weighted_nll(li, pi) : 0.0f;
         hits += (hit && okrow) ? 1.0f : 0.0f;
         __builtin_amdgcn_wave_barrier();
         RLVI_STAMP(5);
@@ -776,7 +782,7 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
         // at least 2.0 into the sum, so the exact check (the words are still in registers) runs only for waves
         // that hold such a row
         bool hit = hit0;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit0 && s >= 2.0f) != 0, 0)) {
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit0 && !(s < 2.0f)) != 0, 0)) {
             int earlier = 0;
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
@@ -804,7 +810,7 @@ __global__ __launch_bounds__(WPB *WAVE, 4) void mstep_bf16w_kernel(
             }
         }
         if (g == 0 && okrow && residuals != nullptr) residuals[ix] = li;
-        acc += okrow ? li * pi : 0.0f;
+        acc += okrow ? weighted_nll(li, pi) : 0.0f;
         hits += (hit && okrow) ? 1.0f : 0.0f;
         __builtin_amdgcn_wave_barrier();
 

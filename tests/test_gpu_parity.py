@@ -135,7 +135,8 @@ def test_mstep_vs_oracle_shapes(B, C, gpu, oracle):
     assert dev_status(gpu[1], gpu[2]) == 0
 
 
-@pytest.mark.parametrize("B,C,dtype", [
+# (row counts: the smallest that select each branch; tests/test_logit_range_gpu.py runs the same list)
+DISPATCH_SHAPES = [
     (70003, 10, "f32"),      # one lane per row, wave tiles (>= 1024 waves: no doubling of the lanes)
     (40001, 101, "f32"),     # rows not a multiple of 16 bytes, >= 32 768 rows: four lanes x 32 single elements
     (33001, 102, "f32"),     # ... x 16 two-element vectors
@@ -164,7 +165,10 @@ def test_mstep_vs_oracle_shapes(B, C, gpu, oracle):
     (1100, 2052, "f32"),     # ... 16-byte vectors, a wave per row
     (130, 4104, "bf16"),     # ... bf16, 8-element vectors
     (257, 1001, "bf16"),     # ... bf16, single elements
-])
+]
+
+
+@pytest.mark.parametrize("B,C,dtype", DISPATCH_SHAPES)
 def test_mstep_dispatch_by_launch_size_vs_oracle(B, C, dtype, gpu, oracle):
     """The launcher picks lanes per row and kernel form by the SIZE of the launch (mstep.hip dispatch_gk /
     launch_mstep: fewer than 1024 waves -> twice the lanes per row; up to 512 tiles -> register rows; the
