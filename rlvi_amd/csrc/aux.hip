@@ -186,7 +186,6 @@ __device__ __forceinline__ double rows16_dot_mfma(const double *__restrict__ X, 
 }
 
 // r_i = (y_i - x_i.theta)^2 -> losses; block partials of {w.r, sum w} -> part
-template <bool MFMA>
 __global__ __launch_bounds__(256) void linreg_resid_kernel(const double *__restrict__ X,
                                                            const double *__restrict__ y,
                                                            const double *__restrict__ theta,
@@ -196,29 +195,15 @@ __global__ __launch_bounds__(256) void linreg_resid_kernel(const double *__restr
                                                            double *__restrict__ part) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double num = 0.0, den = 0.0;
-    if (MFMA) {
-        for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 16; r0 < n; r0 += (int64_t)gridDim.x * 64) {
-            int myrow;
-            const double p = rows16_dot_mfma(X, theta, r0, n, d, myrow);
-            const int64_t i = r0 + myrow;
-            if (myrow >= 0 && i < n) {
-                const double r = (y[i] - p) * (y[i] - p);
-                losses[i] = r;
-                num += w[i] * r;
-                den += w[i];
-            }
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
-            double p = 0.0;
-            for (int64_t j = lane; j < d; j += 64) p += X[i * d + j] * theta[j];
-            p = wave_sum(p);
+    for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 16; r0 < n; r0 += (int64_t)gridDim.x * 64) {
+        int myrow;
+        const double p = rows16_dot_mfma(X, theta, r0, n, d, myrow);
+        const int64_t i = r0 + myrow;
+        if (myrow >= 0 && i < n) {
             const double r = (y[i] - p) * (y[i] - p);
-            if (lane == 0) {
-                losses[i] = r;
-                num += w[i] * r;
-                den += w[i];
-            }
+            losses[i] = r;
+            num += w[i] * r;
+            den += w[i];
         }
     }
     num = wave_sum(num);
@@ -250,26 +235,15 @@ __device__ __forceinline__ double logistic_nll_of(double p) {
     return p >= 0.0 ? log1p(exp(-p)) : -p + log1p(exp(p));
 }
 
-template <bool MFMA>
 __global__ __launch_bounds__(256) void logistic_nll_kernel(const double *__restrict__ X,
                                                            const double *__restrict__ wv, double b,
                                                            int64_t n, int64_t d,
                                                            double *__restrict__ losses) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto nll = [](double p) { return logistic_nll_of(p); };
-    if (MFMA) {
-        for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 16; r0 < n; r0 += (int64_t)gridDim.x * 64) {
-            int myrow;
-            const double p = rows16_dot_mfma(X, wv, r0, n, d, myrow) + b;
-            if (myrow >= 0 && r0 + myrow < n) losses[r0 + myrow] = nll(p);
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
-            double p = 0.0;
-            for (int64_t j = lane; j < d; j += 64) p += X[i * d + j] * wv[j];
-            p = wave_sum(p) + b;
-            if (lane == 0) losses[i] = nll(p);
-        }
+    const int wave = threadIdx.x >> 6;
+    for (int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * 16; r0 < n; r0 += (int64_t)gridDim.x * 64) {
+        int myrow;
+        const double p = rows16_dot_mfma(X, wv, r0, n, d, myrow) + b;
+        if (myrow >= 0 && r0 + myrow < n) losses[r0 + myrow] = logistic_nll_of(p);
     }
 }
 
@@ -308,12 +282,10 @@ extern "C" int rlvi_linreg_losses_f64(const double *X, const double *y, const do
     hipStream_t st = static_cast<hipStream_t>(stream);
     // scratch region (NOT the M-step records, which must stay zero between epochs)
     double *part = reinterpret_cast<double *>(static_cast<char *>(ws) + WS_SCRATCH_OFF);
-    // X.theta on the fp64 matrix cores (16 rows per wave); RLVI_XW_MFMA=0: one wave dot product per row
-    const bool mfma = tune_get("RLVI_XW_MFMA", 1) != 0;
-    int nb = (int)(mfma ? (n + 63) / 64 : (n + 3) / 4);
+    // X.theta on the fp64 matrix cores: 16 rows per wave, 64 per workgroup
+    int nb = (int)((n + 63) / 64);
     if (nb > 256) nb = 256;
-    int rc = mfma ? launch(linreg_resid_kernel<true>, dim3(nb), dim3(256), 0, st, X, y, theta, w, n, d, losses, part)
-                  : launch(linreg_resid_kernel<false>, dim3(nb), dim3(256), 0, st, X, y, theta, w, n, d, losses, part);
+    int rc = launch(linreg_resid_kernel, dim3(nb), dim3(256), 0, st, X, y, theta, w, n, d, losses, part);
     if (rc != 0) return rc;
     int nb2 = (int)((n + 255) / 256);
     if (nb2 > 256) nb2 = 256;
@@ -324,17 +296,15 @@ extern "C" int rlvi_logistic_nll_f64(const double *X, const double *w, double b,
                                      int64_t d, double *losses, void *stream) {
     if (!X || !w || !losses) return RLVI_E_NULL;
     if (n <= 0 || d <= 0) return RLVI_E_SHAPE;
-    const bool mfma = tune_get("RLVI_XW_MFMA", 1) != 0;
-    int nb = (int)(mfma ? (n + 63) / 64 : (n + 3) / 4);
+    int nb = (int)((n + 63) / 64);
     if (nb > 1024) nb = 1024;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (mfma && d >= 128) {
+    if (d >= 128) {
         int nbk = (int)((n + 15) / 16);
         if (nbk > 4096) nbk = 4096;
         return launch(logistic_nll_splitk_kernel, dim3(nbk), dim3(256), 0, st, X, w, b, n, d, losses);
     }
-    return mfma ? launch(logistic_nll_kernel<true>, dim3(nb), dim3(256), 0, st, X, w, b, n, d, losses)
-                : launch(logistic_nll_kernel<false>, dim3(nb), dim3(256), 0, st, X, w, b, n, d, losses);
+    return launch(logistic_nll_kernel, dim3(nb), dim3(256), 0, st, X, w, b, n, d, losses);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -358,7 +328,7 @@ extern "C" int rlvi_stream_copy(void *dst, const void *src, size_t bytes, void *
     if (bytes == 0) return 0;
     const int64_t n16 = (int64_t)(bytes / 16);
     int64_t nb = (n16 + 255) / 256;
-    const int64_t cap = (int64_t)device_info().cus * 4 * tune_get("RLVI_COPY_WPS", 4);     // 16 waves per CU
+    const int64_t cap = (int64_t)device_info().cus * 4 * 4;     // 16 waves per CU
     if (nb > cap) nb = cap;
     return launch(stream_copy_kernel, dim3((unsigned)nb), dim3(256), 0, static_cast<hipStream_t>(stream),
                   static_cast<aux_vu4 *>(dst), static_cast<const aux_vu4 *>(src), n16);

@@ -31,6 +31,7 @@
 namespace rlvi {
 
 constexpr int CDR_BLOCK = 256;
+constexpr int CDR_WGS_PER_CU = 2;            // workgroups per CU of the histogram and apply passes (profiles/r07_cdr.md)
 constexpr int CDR_CHUNK = 4096;              // elements per chunk: four 16-byte pieces per lane
 constexpr int CDR_REPL = 4;                  // copies of the LDS histogram
 constexpr int CDR_BINS0 = 2048, CDR_BINS1 = 1024, CDR_BINS2 = 1024;
@@ -321,7 +322,7 @@ extern "C" int rlvi_cdr_mask_f32(const void *table_dev, int nseg, int64_t total,
     if (scratch_bytes < CDR_SCRATCH_BYTES) return RLVI_E_WS;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const CdrSeg *table = static_cast<const CdrSeg *>(table_dev);
-    int64_t nb = (int64_t)device_info().cus * tune_get("RLVI_CDR_WGS_PER_CU", 2);
+    int64_t nb = (int64_t)device_info().cus * CDR_WGS_PER_CU;
     if (nb > chunks) nb = chunks;
     if (nb < 1) nb = 1;
     const dim3 grid((unsigned)nb), block(CDR_BLOCK);

@@ -2,7 +2,7 @@
 //
 //   * device_info(): CU count of the current device, asked from the runtime once per device --
 //     the launch geometry of every kernel is derived from it, never from a constant.
-//   * coop_blocks(): how many workgroups of a kernel are provably co-resident (occupancy query
+//   * coop_cap(): how many workgroups of a kernel are provably co-resident (occupancy query
 //     x CU count, with the margin MI355X_MICROARCH.md prescribes where the API over-reports);
 //     every kernel whose workgroups wait for each other sizes its exchanging grid with it.
 //   * allow_dyn_lds(): raises a kernel's dynamic-LDS limit beyond 64 KiB, once per kernel and device.

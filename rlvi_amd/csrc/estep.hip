@@ -190,8 +190,6 @@ static int launch_estep(F *res, F *wts, int64_t N, F tol, int maxiter, int32_t *
                                    mstep_scale, &rc))
             return rc;
     }
-    const int force_e = tune_get("RLVI_ESTEP_E", 0);
-    const int force_b = tune_get("RLVI_ESTEP_BLOCK", 0);
     auto groups = [&](int64_t blk, int e) { return (N + blk * e - 1) / (blk * e); };
     const int extra = mstep_out != nullptr ? 1 : 0;
     // every geometry is admitted only if all its workgroups (+ the epoch-end reduction workgroup)
@@ -207,11 +205,8 @@ static int launch_estep(F *res, F *wts, int64_t N, F tol, int maxiter, int32_t *
                           maxiter, out_iters, trace, ws, mstep_out, mstep_scale);                \
     } while (0)
     const int lim = MAX_COOP_WG - 1;    // exchange slots, one kept for the epoch-end reduction workgroup
-    if (force_b == 256 || force_b == 0) {
-        if (force_e == 8 || !force_e) RLVI_LAUNCH(8, 256, lim / 4);
-        if (force_e == 16 || !force_e) RLVI_LAUNCH(16, 256, lim / 4);
-    }
-    if (force_e == 4) RLVI_LAUNCH(4, 1024, lim);
+    RLVI_LAUNCH(8, 256, lim / 4);
+    RLVI_LAUNCH(16, 256, lim / 4);
     RLVI_LAUNCH(8, 1024, lim);
     RLVI_LAUNCH(16, 1024, lim);
     if constexpr (sizeof(F) == 4) {

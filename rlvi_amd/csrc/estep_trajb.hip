@@ -34,11 +34,9 @@ namespace rlvi {
 //  processes share the device)
 // (measured and not kept, round 3: 512-thread workgroups whose second four waves hold no samples and only take
 //  their share of the nodes in the sums, as the in-batch kernel's spare waves do -- 22.1 against 21.9 us per step)
-#ifndef RLVI_TB_MINW
-#define RLVI_TB_MINW 3
-#endif
+constexpr int TB_MINW = 3;      // waves per SIMD the one-sample 256-thread form must allow
 template <int E, int TB_BLOCK>
-__global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMPS) ? RLVI_TB_MINW : 1) void estep_trajb_kernel(
+__global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMPS) ? TB_MINW : 1) void estep_trajb_kernel(
     float *__restrict__ res, float *__restrict__ wts, void *ws, int64_t N, int64_t Nall, int Ls, int G, int K,
     int flags, float tol, int32_t *__restrict__ out_iters, float *__restrict__ trace,
     float *__restrict__ mstep_out, double mstep_scale, unsigned long long *__restrict__ dbg,
@@ -148,23 +146,18 @@ int try_launch_estep_trajb(float *res, float *wts, int64_t N, float tol, int max
                            int32_t *out_iters, float *trace, void *ws, hipStream_t st,
                            float *mstep_out, double mstep_scale, int *rc, int64_t n_all, int sharded,
                            int dry_run) {
-    const int mode = tune_get("RLVI_ESTEP_TRAJB", 1);
     // (round 3: from 64 samples on -- the solve costs its ~10.5 us whatever N is, the iterative kernel 0.8-1.8 us
     //  per iteration: N = 256 16.5 -> 12.0 us, 1024 20.6 -> 12.3, 3000 37.9 -> 12.4 with the copy kernel of the
     //  timing loop; rounds 1-2 had started at 4096 because the slices of their node-per-workgroup form needed it)
-    const int64_t nmin = tune_get("RLVI_ESTEP_TRAJB_NMIN", 64);
-    if (mode == 0 || maxiter < 1 || maxiter > TJ_MAXK || N < nmin) return 0;
-    const int debug = tune_get("RLVI_TJ_DEBUG", 0);
-    // 256 threads measured 2-3 us per call ahead up to N = 262 144, level at 524 288, 1 us behind
-    // from 1e6 on (whole step / eager call, hipGraph): 512 threads only for slices beyond 4096
-    const int blk = tune_get("RLVI_TB_BLOCK", 0);
-    unsigned long long *dbg = (debug && !dry_run) ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
+    constexpr int64_t TB_NMIN = 64;
+    if (maxiter < 1 || maxiter > TJ_MAXK || N < TB_NMIN) return 0;
+    const TbLab lab = tb_lab_args(ws, dry_run != 0);
     const int64_t Nall = sharded ? n_all : N;
     PeerTable *pt = (sharded && !dry_run) ? reinterpret_cast<PeerTable *>(static_cast<char *>(ws) + WS_PEER_OFF) : nullptr;
     // TBF_VERIFY: always run the verification round (lab knob); TBF_COLD: ignore the previous call's trajectory (the
     // caller's workspace option "cold_start": every call as the reference's loop starts it, train_rlvi.py:29);
     // TBF_SHARDED: the state of sharded calls (pt != nullptr in the kernel)
-    const int flags = (tune_get("RLVI_TJ_VERIFY", 0) ? TBF_VERIFY : 0) |
+    const int flags = (lab.verify ? TBF_VERIFY : 0) |
                       ((!sharded && !dry_run && ws_option(ws, WSOPT_COLD_START, 0)) ? TBF_COLD : 0) |
                       (pt != nullptr ? TBF_SHARDED : 0);
     int launched = 0;
@@ -186,7 +179,7 @@ int try_launch_estep_trajb(float *res, float *wts, int64_t N, float tol, int max
         if (G >= TJ_MAXK && L <= (int64_t)(E_) * (B_)) {                                          \
             if (!dry_run)                                                                         \
                 *rc = launch(kern, dim3((unsigned)G), dim3(B_), 0, st, res, wts, ws, N, Nall, (int)L, G,    \
-                             maxiter, flags, tol, out_iters, trace, mstep_out, mstep_scale, dbg, pt); \
+                             maxiter, flags, tol, out_iters, trace, mstep_out, mstep_scale, lab.dbg, pt); \
             else                                                                                  \
                 *rc = 0;                                                                          \
             launched = 1;                                                                         \
@@ -196,16 +189,15 @@ int try_launch_estep_trajb(float *res, float *wts, int64_t N, float tol, int max
     // (7 granules with the third- and fourth-order sums, rlvi_trajb.h) and the recurrence variant hang on
     // the workgroup size, and the ranks' shards -- hence their geometries -- may differ: with one
     // workgroup size everywhere every rank pushes and polls the same records and runs the same chain.
-    const bool only256 = sharded || blk == 256;
-    const bool only512 = !sharded && blk == 512;
-    if (!only512) {
-        RLVI_TB(1, 256); RLVI_TB(2, 256); RLVI_TB(3, 256); RLVI_TB(4, 256); RLVI_TB(6, 256); RLVI_TB(8, 256);
-        RLVI_TB(10, 256); RLVI_TB(12, 256); RLVI_TB(16, 256);
-    }
+    // Otherwise 256 threads measured 2-3 us per call ahead up to N = 262 144, level at 524 288, 1 us behind
+    // from 1e6 on (whole step / eager call, hipGraph): 512 threads only for slices beyond 4096.
+    const bool only256 = sharded != 0;
+    RLVI_TB(1, 256); RLVI_TB(2, 256); RLVI_TB(3, 256); RLVI_TB(4, 256); RLVI_TB(6, 256); RLVI_TB(8, 256);
+    RLVI_TB(10, 256); RLVI_TB(12, 256); RLVI_TB(16, 256);
     if (!only256) {
         RLVI_TB(2, 512); RLVI_TB(4, 512); RLVI_TB(6, 512); RLVI_TB(8, 512); RLVI_TB(12, 512); RLVI_TB(16, 512);
     }
-    if (!only512) { RLVI_TB(24, 256); RLVI_TB(32, 256); }
+    RLVI_TB(24, 256); RLVI_TB(32, 256);
 #undef RLVI_TB
     return launched;
 }

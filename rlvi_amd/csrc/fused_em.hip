@@ -557,6 +557,7 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
                         int64_t B, int64_t C, float inv_scale, float tol, int maxiter, float *grad,
                         int64_t ldg, float *out, int32_t *out_iters, void *ws, hipStream_t st, int *rc) {
     if (tune_get("RLVI_FUSED_EM", 1) == 0) return 0;
+    const TbLab lab = tb_lab_args(ws);
     if (grad != nullptr && ld == C && ldg == C && C <= FR_CMAX && B >= 64 && maxiter >= 1 && maxiter <= TJ_MAXK) {
         // short rows: a row per thread, the stand-alone E-step's grid (its admission rule too: every
         // exchanging workgroup co-resident, node k reduced by workgroup k)
@@ -565,10 +566,8 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         if (G > TB_G) G = TB_G;
         const int64_t L = G > 0 ? (B + G - 1) / G : 0;      // rows of a workgroup
         if (G >= TJ_MAXK && L <= FR_THREADS) {
-            const int debug = tune_get("RLVI_TJ_DEBUG", 0);
-            unsigned long long *dbg = debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
             *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, ws, B, (int)C,
-                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, tune_get("RLVI_TJ_VERIFY", 0));
+                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, lab.dbg, G, lab.verify);
             return 1;
         }
         return 0;
@@ -578,16 +577,13 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         !(((uintptr_t)logits & 15) || ((uintptr_t)grad & 15))) {
         // wide rows, too few of them for the LDS-resident kernel below: four lanes per row, up to 64 rows per
         // workgroup on as many workgroups as are co-resident (at most 256)
-        const int debug = tune_get("RLVI_TJ_DEBUG", 0);
-        unsigned long long *dbg = debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
-        const int verify = tune_get("RLVI_TJ_VERIFY", 0);
         auto go = [&](auto kern) {
             int G = coop_cap(kern, FR_THREADS);
             if (G > TB_G) G = TB_G;
             const int64_t L = G > 0 ? (B + G - 1) / G : 0;
             if (G < TJ_MAXK || L > FR_THREADS / 4) return 0;   // node k is reduced by workgroup k; 64 rows each
             *rc = launch(kern, dim3((unsigned)G), dim3(FR_THREADS), 0, st, logits, labels, loss_rows, pi, ws, B, (int)C,
-                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, verify);
+                         (int)L, maxiter, inv_scale, tol, grad, out, out_iters, lab.dbg, G, lab.verify);
             return 1;
         };
         if (C <= 64 ? go(fused_em_rows4_kernel<4>) : go(fused_em_rows4_kernel<8>)) return 1;
@@ -601,9 +597,6 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
     if (G64 < TJ_MAXK || G64 > TB_G) return 0;      // node k of the trajectory is reduced by workgroup k
     const int G = (int)G64;
     const int nv = (int)C / 4, k = (nv + 3) / 4;
-    const int debug = tune_get("RLVI_TJ_DEBUG", 0);
-    unsigned long long *dbg = debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr;
-    const int verify = tune_get("RLVI_TJ_VERIFY", 0);
     int launched = 0;
 #define RLVI_FE(K_, X_)                                                                              \
     do {                                                                                             \
@@ -612,7 +605,7 @@ int try_launch_fused_em(const float *logits, int64_t ld, const int64_t *labels, 
         if (allow_dyn_lds(kern, lds) != 0) break;                                                    \
         if (coop_cap(kern, FE_THREADS, lds) < G) break;     /* all G workgroups must be resident */  \
         *rc = launch(kern, dim3((unsigned)G), dim3(FE_THREADS), lds, st, logits, labels, loss_rows, pi, ws, B, \
-                     (int)C, maxiter, inv_scale, tol, grad, out, out_iters, dbg, G, verify);         \
+                     (int)C, maxiter, inv_scale, tol, grad, out, out_iters, lab.dbg, G, lab.verify); \
         launched = 1;                                                                                \
     } while (0)
     if (k <= 4) RLVI_FE(4, false);

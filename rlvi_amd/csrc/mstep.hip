@@ -97,7 +97,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
         for (int k = 0; k < KMAX; ++k) {
             const int col = (k * G + g) * V;
             live[k] = k < kact && col < C;
-            VecIO<T, V>::load_stream(zrow + (live[k] ? col : g * V), v[k]);
+            VecIO<T, V>::load(zrow + (live[k] ? col : g * V), v[k]);
         }
         __builtin_amdgcn_sched_barrier(0);
         ix = idx != nullptr ? ix : first_row + rr;    // idx == NULL: identity (in-batch E+M), counted from the batch start
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_kernel(
                         if (col + j == y) p -= gs;
                         o[j] = p;
                     }
-                    VecIO<T, V>::store_stream(grow + col, o);
+                    VecIO<T, V>::store(grow + col, o);
                 }
             }
         }
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
                             if (k * V + j == y) p -= gs;
                             o[j] = p;
                         }
-                        VecIO<T, V>::store_stream(grow + (size_t)k * V, o);
+                        VecIO<T, V>::store(grow + (size_t)k * V, o);
                     }
                 }
             }
@@ -373,16 +373,15 @@ __global__ __launch_bounds__(MSTEP_THREADS) void mstep_longrow_kernel(
 #else
 #define RLVI_STAMP(k) do { } while (0)
 #endif
-#ifndef RLVI_MSTEP_WAVE_MINW
-#define RLVI_MSTEP_WAVE_MINW 4    // waves per SIMD the register allocation must allow (LDS allows 5)
-#endif
+constexpr int MSTEP_WAVE_MINW = 4;    // waves per SIMD the register allocation must allow (LDS allows 5)
+constexpr int MSTEP_WAVE_WPC = 16;    // waves per CU that stride over the wave tiles
 
 struct FMaxF { __device__ __forceinline__ float operator()(float a, float b) const { return __builtin_fmaxf(a, b); } };
 
 // EXACT: the host guarantees ceil(ceil(C/V)/G) == KMAX, so only a lane's LAST slot can lie past
 // the end of the row and (for 16-byte vectors) only the last load / store piece can be partial.
 template <typename T, int V, int G, int KMAX, int WPB, bool EXACT>
-__global__ __launch_bounds__(WPB *WAVE, RLVI_MSTEP_WAVE_MINW) void mstep_wave_kernel(
+__global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     const T *__restrict__ logits, const int64_t *__restrict__ labels,
     const int64_t *__restrict__ idx, int64_t nfull, int C, int hold_ticks, const float *__restrict__ weights,
     int64_t N, float *__restrict__ residuals, float inv_scale,
@@ -861,7 +860,6 @@ __global__ __launch_bounds__(256) void mstep_finalize_kernel(double *__restrict_
 struct MstepKnobs {
     int form;        // RLVI_MSTEP_FORM: see launch_mstep
     int force_g;     // RLVI_MSTEP_G: lanes per row, 0 = the dispatch rules decide
-    int wpc;         // RLVI_MSTEP_WPC: waves per CU that stride over the wave tiles
     int cuwide;      // RLVI_MSTEP_CUWIDE: the 16-wave barrier form where its conditions hold
     int hold, gen;   // RLVI_MSTEP_HOLD, RLVI_MSTEP_GEN: see launch_mstep
 };
@@ -892,11 +890,11 @@ struct MstepCall {
     double inv_rows100;
     int cus;
 
-    // Workgroups of `wpb` waves for `tiles` wave tiles: `wpc` waves per CU stride over the tiles (one tile each
+    // Workgroups of `wpb` waves for `tiles` wave tiles: MSTEP_WAVE_WPC waves per CU stride over the tiles (one tile each
     // at the bench size), and every workgroup owns a record
     int64_t tile_grid(int64_t tiles, int wpb) const {
         int64_t nb = (tiles + wpb - 1) / wpb;
-        int64_t cap = ((int64_t)knobs.wpc * cus + wpb - 1) / wpb;
+        int64_t cap = ((int64_t)MSTEP_WAVE_WPC * cus + wpb - 1) / wpb;
         if (cap > MSTEP_MAX_BLOCKS) cap = MSTEP_MAX_BLOCKS;
         return nb > cap ? cap : nb;
     }
@@ -1159,7 +1157,6 @@ static int mstep_entry(const T *logits, int64_t ld, const int64_t *labels, const
     c.out = out; c.ws = ws; c.st = static_cast<hipStream_t>(stream);
     c.knobs.form = tune_get("RLVI_MSTEP_FORM", -1);
     c.knobs.force_g = tune_get("RLVI_MSTEP_G", 0);
-    c.knobs.wpc = tune_get("RLVI_MSTEP_WPC", 16);
     c.knobs.cuwide = tune_get("RLVI_MSTEP_CUWIDE", 1);
     c.knobs.hold = tune_get("RLVI_MSTEP_HOLD", ws_option(ws, WSOPT_LOGITS_FROM_HBM, 0) ? -1 : 0);
     c.knobs.gen = tune_get("RLVI_MSTEP_GEN", -1);

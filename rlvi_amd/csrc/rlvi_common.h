@@ -38,15 +38,8 @@ void ws_options_forget(const void *ws);
 void ws_note_mstep(const void *ws, int code);      // which M-step form the last launch on `ws` took (tests)
 // Workgroups that are provably co-resident given the occupancy API's answer for one CU.
 int coop_blocks_from_occupancy(int per_cu_api, int block_threads, int cus);
-// Number of co-resident workgroups of `kernel` (block threads, dynamic LDS bytes) on this device.
-template <class K>
-inline int coop_blocks(K kernel, int block_threads, size_t dyn_lds) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, dyn_lds) != hipSuccess)
-        per_cu = 0;
-    return coop_blocks_from_occupancy(per_cu, block_threads, device_info().cus);
-}
-// Same, cached per (kernel, device): one occupancy query per kernel instantiation and device.
+// Number of co-resident workgroups of `kernel` (block threads, dynamic LDS bytes) on this device, cached per
+// (kernel, device): one occupancy query per kernel instantiation and device.
 int coop_cap_cached(const void *kernel, int block_threads, size_t dyn_lds);
 template <class K>
 inline int coop_cap(K kernel, int block_threads, size_t dyn_lds = 0) {
@@ -118,10 +111,7 @@ constexpr size_t WS_PART2_OFF = WS_PART_OFF + WS_PART_BYTES;
 constexpr size_t WS_XCHG3A_OFF = WS_PART2_OFF + WS_PART_BYTES;
 constexpr size_t WS_XCHG3A_BYTES = 2ull * 64 * MAX_COOP_WG * XCHG3_GRANULES * 8;   // 2 MiB
 constexpr size_t WS_XCHG3B_OFF = WS_XCHG3A_OFF + WS_XCHG3A_BYTES;
-#ifndef RLVI_XCHG3B_REPLICAS
-#define RLVI_XCHG3B_REPLICAS 8
-#endif
-constexpr int XCHG3B_REPLICAS = RLVI_XCHG3B_REPLICAS;     // the per-node totals are published in 8 copies (one per 32 pollers)
+constexpr int XCHG3B_REPLICAS = 8;     // the per-node totals are published in 8 copies (one per 32 pollers)
 constexpr size_t WS_XCHG3B_BYTES = 2ull * XCHG3B_REPLICAS * 64 * XCHG3_GRANULES * 8;   // 64 KiB
 // fourth exchange region (radix-descent threshold, threshold.hip): 32-byte records of four self-tagged
 // granules {count, min key, sum lo, sum hi}; a workgroup publishes up to 2 x 256 of them per exchange
@@ -274,17 +264,8 @@ __device__ __forceinline__ int group_min_i(int v) { return group_allreduce<G>(v,
 
 // exp(d) for d = z - max <= 0: one multiply by log2(e) and v_exp_f32.  d is an exact-to-1-ulp
 // fp32 difference, so the argument error is |d|*log2(e)*2^-24: below 1e-7 relative for every
-// term that is not already negligible against sum >= 1 (set RLVI_MSTEP_FAST_EXP=0 for ocml expf).
-#ifndef RLVI_MSTEP_FAST_EXP
-#define RLVI_MSTEP_FAST_EXP 1
-#endif
-__device__ __forceinline__ float mexp(float x) {
-#if RLVI_MSTEP_FAST_EXP
-    return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
-#else
-    return expf(x);
-#endif
-}
+// term that is not already negligible against sum >= 1.
+__device__ __forceinline__ float mexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
 // Sums the per-block partial records in a fixed order and writes the four output scalars
 // (scaled by `scale`: 1 for a single batch, 1/batches for an epoch); optionally clears them.
@@ -376,22 +357,12 @@ struct Half<f16_t> {                                              // fp16
     }
 };
 
-#ifndef RLVI_MSTEP_NT
-#define RLVI_MSTEP_NT 0   // the *_stream forms (the M-step's): bit 0 nontemporal loads, bit 1 nontemporal stores
-#endif
 typedef float vf4 __attribute__((ext_vector_type(4)));
 
 // V consecutive elements of T <-> fp32: fp32 vectors of 1, 2 or 4, 2-byte vectors (bf16, fp16) of 1, 2, 4 or 8
 // elements, widened and narrowed through Half<T>.  V elements must be V * sizeof(T)-byte aligned (vec_fits).
 template <typename T, int V>
 struct VecIO;
-
-// default streaming forms = the plain forms (specialisations below override where it pays)
-template <typename T, int V, class Self>
-struct VecIOBase {
-    static __device__ __forceinline__ void load_stream(const T *p, float (&v)[V]) { Self::load(p, v); }
-    static __device__ __forceinline__ void store_stream(T *p, const float (&v)[V]) { Self::store(p, v); }
-};
 
 template <>
 struct VecIO<float, 4> {
@@ -402,26 +373,9 @@ struct VecIO<float, 4> {
     static __device__ __forceinline__ void store(float *p, const float (&v)[4]) {
         *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
     }
-    // streaming forms: read-once / write-once data bypasses cache retention (`nt`)
-    static __device__ __forceinline__ void load_stream(const float *p, float (&v)[4]) {
-#if RLVI_MSTEP_NT & 1
-        const vf4 t = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(p));
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-#else
-        load(p, v);
-#endif
-    }
-    static __device__ __forceinline__ void store_stream(float *p, const float (&v)[4]) {
-#if RLVI_MSTEP_NT & 2
-        const vf4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<vf4 *>(p));
-#else
-        store(p, v);
-#endif
-    }
 };
 template <>
-struct VecIO<float, 2> : VecIOBase<float, 2, VecIO<float, 2>> {
+struct VecIO<float, 2> {
     static __device__ __forceinline__ void load(const float *p, float (&v)[2]) {
         const float2 t = *reinterpret_cast<const float2 *>(p);
         v[0] = t.x; v[1] = t.y;
@@ -431,13 +385,13 @@ struct VecIO<float, 2> : VecIOBase<float, 2, VecIO<float, 2>> {
     }
 };
 template <>
-struct VecIO<float, 1> : VecIOBase<float, 1, VecIO<float, 1>> {
+struct VecIO<float, 1> {
     static __device__ __forceinline__ void load(const float *p, float (&v)[1]) { v[0] = *p; }
     static __device__ __forceinline__ void store(float *p, const float (&v)[1]) { *p = v[0]; }
 };
 // 2-byte elements (T = uint16_t: bf16, T = f16_t: fp16): widened to fp32 and narrowed back through Half<T>
 template <typename T>
-struct VecIO<T, 8> : VecIOBase<T, 8, VecIO<T, 8>> {
+struct VecIO<T, 8> {
     static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
         const uint4 t = *reinterpret_cast<const uint4 *>(p);
         const uint32_t w[4] = {t.x, t.y, t.z, t.w};
@@ -456,7 +410,7 @@ struct VecIO<T, 8> : VecIOBase<T, 8, VecIO<T, 8>> {
     }
 };
 template <typename T>
-struct VecIO<T, 4> : VecIOBase<T, 4, VecIO<T, 4>> {
+struct VecIO<T, 4> {
     static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
         const uint2 t = *reinterpret_cast<const uint2 *>(p);
         v[0] = Half<T>::lo(t.x); v[1] = Half<T>::hi(t.x);
@@ -470,7 +424,7 @@ struct VecIO<T, 4> : VecIOBase<T, 4, VecIO<T, 4>> {
     }
 };
 template <typename T>
-struct VecIO<T, 2> : VecIOBase<T, 2, VecIO<T, 2>> {
+struct VecIO<T, 2> {
     static __device__ __forceinline__ void load(const T *p, float (&v)[2]) {
         const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
         v[0] = Half<T>::lo(t); v[1] = Half<T>::hi(t);
@@ -480,7 +434,7 @@ struct VecIO<T, 2> : VecIOBase<T, 2, VecIO<T, 2>> {
     }
 };
 template <typename T>
-struct VecIO<T, 1> : VecIOBase<T, 1, VecIO<T, 1>> {
+struct VecIO<T, 1> {
     static __device__ __forceinline__ void load(const T *p, float (&v)[1]) {
         v[0] = Half<T>::widen(*reinterpret_cast<const uint16_t *>(p));
     }

@@ -7,9 +7,7 @@ namespace rlvi {
 
 constexpr int TJ_MAXK = 64;
 constexpr float TJ_ACCEPT = 1e-6f;
-#ifndef RLVI_TJ_TRUST
-#define RLVI_TJ_TRUST 0.25f
-#endif
+constexpr float TJ_TRUST = 0.25f;     // trust region of the local model, relative to the node (tj_chain)
 
 struct TrajState {
     long long n;
@@ -329,7 +327,7 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
     //  data-to-data drift of 2-7 % stays on this path; beyond it the local model converges one
     //  node per round at worst)
     const bool inside = !cold && (!(has && lane < steps) ||
-                        (fabsf(rnew_l - rn) <= RLVI_TJ_TRUST * rn && avg_l > 0.0f && avg_l < 0.999999f));
+                        (fabsf(rnew_l - rn) <= TJ_TRUST * rn && avg_l > 0.0f && avg_l < 0.999999f));
     if (!__all(inside)) {
         // Cold or poor guesses: the nodes are far from the trajectory, but together they sample
         // S(r) over its whole range.  s(u) = mean(pi) as a function of u = log r is a sum of

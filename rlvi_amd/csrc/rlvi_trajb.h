@@ -17,15 +17,25 @@ typedef unsigned int tb_vu4 __attribute__((ext_vector_type(4)));
 // Workgroup size: 256 threads = one wave per SIMD (the per-wave butterflies are a fixed cost per
 // wave and chunk, so fewer, fatter waves win as long as the slice fits the registers); the main loop
 // has no memory operations to hide and eight independent nodes of instruction-level parallelism.
-#ifndef RLVI_TB_G
-#define RLVI_TB_G 256
-#endif
 // 256 exchanging workgroups (the epoch-end reduction rides on the last one): at the bench size a slice is
 // exactly one sample per thread (32.6 us per step against 33.9 with 240).
-constexpr int TB_G = RLVI_TB_G;      // exchanging workgroups at most (= exchange slots per node)
+constexpr int TB_G = 256;            // exchanging workgroups at most (= exchange slots per node)
 constexpr int TB_CHUNK = 8;
 constexpr int TB_NV = 8;             // values of a record: {S, P, Q, D, min, R3, R4, -}
 constexpr int TB_PER = (TB_G + WAVE - 1) / WAVE;   // polling waves of a stage-A gather
+
+// Host: the lab arguments of a launch that runs the solve.  dbg: where the -DRLVI_STAMPS=1 build leaves its stamps
+// and dumps (the workspace's scratch region) when RLVI_TJ_DEBUG is set -- never for a dry run, which has no
+// workspace; verify: RLVI_TJ_VERIFY, always run the verification round.
+struct TbLab {
+    unsigned long long *dbg;
+    int verify;
+};
+inline TbLab tb_lab_args(void *ws, bool dry_run = false) {
+    const bool debug = tune_get("RLVI_TJ_DEBUG", 0) != 0 && !dry_run;
+    return {debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr,
+            tune_get("RLVI_TJ_VERIFY", 0)};
+}
 
 // Node-split sums (slices up to TB_NSPLIT_MAXS samples per workgroup): the slice's e = exp(-(l - min)) and
 // the caller's pi are staged through LDS so that EVERY wave sees all samples and the waves share out the

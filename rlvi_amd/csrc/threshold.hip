@@ -975,34 +975,30 @@ static int launch_threshold(float *w, int64_t N, float alpha, float *thr, uint8_
     // G = 1 (no exchange) up to 1024 keys; 64 workgroups (fewest participants per exchange) while a
     // slice fits 8 keys per thread, then 128, then 256; every G > 1 only if the occupancy query says
     // that many workgroups are co-resident on this device
-    if (tune_get("RLVI_THR_RADIX", 1)) {
-        const int force_g = tune_get("RLVI_THR_G", 0);
-        if (N <= 1024 && !force_g && !sharded) RLVI_THQ(4, 1);
-        // the histogram costs about 1 us per key slot of a thread (LDS atomics), an exchange -- and the key
-        // list's hop -- grows with the number of publishing workgroups: 64 workgroups up to two keys per
-        // thread, 128 up to sixteen, then 256 (round 3, criterion alone: N = 32 768 16.5 / 17.3 us for 64 / 128;
-        // 65 536 18.5 / 18.1 / 20.4 for 64 / 128 / 256; 262 144 21.3 / 23.0 and 524 288 24.0 / 24.4 for 128 / 256;
-        // 1 048 576 29.0 / 26.7)
-        for (int G = 64; G <= 256; G *= 2) {
-            if (force_g && G != force_g) continue;
-            const int64_t L = (N + G - 1) / G;
-            const int emax = force_g ? 32 : (G == 64 ? 2 : G == 128 ? 16 : 32);
-            if (L > (int64_t)THQ_BLOCK * emax) continue;
-            if (L <= THQ_BLOCK * 1) RLVI_THQ(1, G);
-            else if (L <= THQ_BLOCK * 2) RLVI_THQ(2, G);
-            else if (L <= THQ_BLOCK * 4) RLVI_THQ(4, G);
-            else if (L <= THQ_BLOCK * 8) RLVI_THQ(8, G);
-            else if (L <= THQ_BLOCK * 16) RLVI_THQ(16, G);
-            else if (L <= THQ_BLOCK * 32) RLVI_THQ(32, G);
-        }
-        // (fewer co-resident workgroups than the preferred geometry asks for: any geometry that fits)
-        for (int G = 64; G <= 256 && !launched && !force_g; G *= 2) {
-            const int64_t L = (N + G - 1) / G;
-            if (L <= THQ_BLOCK * 8) RLVI_THQ(8, G);
-            else if (L <= THQ_BLOCK * 32) RLVI_THQ(32, G);
-        }
-        if (N <= 8192 && !sharded) RLVI_THQ(32, 1);          // (fewer than 64 co-resident workgroups: one workgroup)
+    if (N <= 1024 && !sharded) RLVI_THQ(4, 1);
+    // the histogram costs about 1 us per key slot of a thread (LDS atomics), an exchange -- and the key
+    // list's hop -- grows with the number of publishing workgroups: 64 workgroups up to two keys per
+    // thread, 128 up to sixteen, then 256 (round 3, criterion alone: N = 32 768 16.5 / 17.3 us for 64 / 128;
+    // 65 536 18.5 / 18.1 / 20.4 for 64 / 128 / 256; 262 144 21.3 / 23.0 and 524 288 24.0 / 24.4 for 128 / 256;
+    // 1 048 576 29.0 / 26.7)
+    for (int G = 64; G <= 256; G *= 2) {
+        const int64_t L = (N + G - 1) / G;
+        const int emax = G == 64 ? 2 : G == 128 ? 16 : 32;
+        if (L > (int64_t)THQ_BLOCK * emax) continue;
+        if (L <= THQ_BLOCK * 1) RLVI_THQ(1, G);
+        else if (L <= THQ_BLOCK * 2) RLVI_THQ(2, G);
+        else if (L <= THQ_BLOCK * 4) RLVI_THQ(4, G);
+        else if (L <= THQ_BLOCK * 8) RLVI_THQ(8, G);
+        else if (L <= THQ_BLOCK * 16) RLVI_THQ(16, G);
+        else if (L <= THQ_BLOCK * 32) RLVI_THQ(32, G);
     }
+    // (fewer co-resident workgroups than the preferred geometry asks for: any geometry that fits)
+    for (int G = 64; G <= 256 && !launched; G *= 2) {
+        const int64_t L = (N + G - 1) / G;
+        if (L <= THQ_BLOCK * 8) RLVI_THQ(8, G);
+        else if (L <= THQ_BLOCK * 32) RLVI_THQ(32, G);
+    }
+    if (N <= 8192 && !sharded) RLVI_THQ(32, 1);          // (fewer than 64 co-resident workgroups: one workgroup)
 #undef RLVI_THQ
     if (launched) return rc;
     if (sharded) return RLVI_E_LIMIT;            // (the one-workgroup forms see one rank's weights only)
