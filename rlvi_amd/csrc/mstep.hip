@@ -394,7 +394,11 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     // The compiler puts its own fetch of the arguments past the preloaded ones at the top of the kernel, in front
     // of anything written here.  So this build does not touch those parameters: it reads them (and the grid size,
     // which the runtime appends to them) from the argument block itself, through a pointer that exists only behind
-    // the stamp (offsets = the signature's layout).
+    // the stamp (offsets = the signature's layout).  NOT the grid size: the runtime appends the hidden arguments only
+    // to a kernel whose code asks for them, and a kernel that reads them through this pointer alone has an argument
+    // block that ends at gen_ticks -- byte 128 is past it, and a tile loop that advances by whatever lies there does
+    // not end when that is zero.  The forms that stride over tiles take gridDim.x as every build does (their entry
+    // is not what the stamps are for); the ENTRY_FIRST form has one tile per wave and does not use it.
     unsigned long long t_entry;
     typedef const __attribute__((address_space(4))) char *ms_ka_t;
     ms_ka_t ka = (ms_ka_t)__builtin_amdgcn_kernarg_segment_ptr();
@@ -411,7 +415,7 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     accum = MS_LATE(int, 104);
     inv_rows100 = MS_LATE(double, 112);
     gen_ticks = MS_LATE(int, 120);
-    const unsigned grid_x = MS_LATE(unsigned, 128);
+    const unsigned grid_x = (WPB == 16 && sizeof(T) == 4) ? 0u : gridDim.x;
 #undef MS_LATE
 #else
     const unsigned grid_x = gridDim.x;
@@ -435,8 +439,25 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     bool first_tile = true;
 #endif
 
+    // ENTRY_FIRST (the 16-wave fp32 form, one tile per wave: the launch is as long as a wave's own latency): in front
+    // of the first tile's loads stands only what their ADDRESSES need, and nothing that hangs on an argument past
+    // the preloaded ones.  Every wave of a SIMD issues its prologue before the SIMD's last wave has asked HBM for
+    // anything, so an instruction here is paid four times.  The lane's LDS geometry (slot_off, live, row_off), the
+    // range checks' constants and the gradient's gain (later arguments and, under a GradScaler, a load) are first
+    // used in phase B, behind a wait of microseconds: they are computed behind the issue of the loads and the
+    // CU-wide barrier, from copies of lane / wave / C that pass through an empty asm there, so that the compiler
+    // cannot hoist them in front of the loop again; the later arguments pass through the same asm.  The other
+    // forms keep the gain and the loop invariants in front of the loop: they stride over several tiles or sit at a
+    // register bound, where carrying these through the loop costs a register, i.e. a wave per SIMD or a spill.
+    constexpr bool ENTRY_FIRST = WPB == 16 && sizeof(T) == 4;
+
     // loop-invariant per-lane geometry
-    unsigned dma_off[NI];                                         // byte offset of this lane's chunk of piece i
+    // Byte offset of this lane's chunk of piece i, 32 bits: the ENTRY_FIRST form's LOADS take a wave-uniform (scalar)
+    // base, this offset and an immediate.  With EXACT16 the pieces 0 .. NI-2 are lane * 16 + i * 1024 -- one register,
+    // the piece in the immediate as far as the instruction's offset field reaches -- and only the last one is clamped.
+    // (The gradient's stores are as they were: flat stores on 64-bit VGPR addresses -- `grad` passes through the
+    //  empty asm behind the loads, where the compiler loses its address space.)
+    unsigned dma_off[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         int c = i * WAVE + lane;
@@ -445,23 +466,21 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     }
     int slot_off[KMAX];                                           // LDS byte offset of slot k inside the slice
     bool live[KMAX];
+    int row_off = 0;
+    // (lane_l, wave_l, C_l: what phases B and C see of the lane, the wave and C; ENTRY_FIRST re-reads them behind the barrier)
+    int lane_l = lane, wave_l = wave, C_l = C, g_l = g, sub_l = sub, nv_l = nv;
+    char *wtile_l = wtile;
+    if constexpr (!ENTRY_FIRST) {
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        const int vec = k * G + g;
-        live[k] = (EXACT && k < KMAX - 1) || vec < nv;
-        slot_off[k] = (sub * C + (live[k] ? vec : nv - 1) * V) * (int)sizeof(T);
+        for (int k = 0; k < KMAX; ++k) {
+            const int vec = k * G + g;
+            live[k] = (EXACT && k < KMAX - 1) || vec < nv;
+            slot_off[k] = (sub * C + (live[k] ? vec : nv - 1) * V) * (int)sizeof(T);
+        }
+        row_off = sub * C * (int)sizeof(T);
     }
-    const int row_off = sub * C * (int)sizeof(T);
     const int64_t *idxp = idx != nullptr ? idx : labels;
     const unsigned sub8 = (unsigned)sub * 8u;
-    // ENTRY_FIRST (the 16-wave fp32 form, one tile per wave: the launch is as long as a wave's own latency): nothing
-    // that hangs on an argument past the preloaded ones is touched in front of the first tile's loads.  The
-    // gradient's gain (later arguments and, under a GradScaler, a load) is taken behind their issue, and the later
-    // arguments pass through an empty asm inside the loop so that nothing derived from them is hoisted in front of
-    // it.  The other forms keep the gain and the loop invariants in front of the loop: they stride over several
-    // tiles or sit at a register bound, where carrying these through the loop costs a register, i.e. a wave per
-    // SIMD or a spill.
-    constexpr bool ENTRY_FIRST = WPB == 16 && sizeof(T) == 4;
     float gscale = ENTRY_FIRST ? 0.0f : grad_gain(inv_scale, grad_scale);
     bool have_gain = !ENTRY_FIRST;
 
@@ -487,11 +506,20 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     // (The launcher takes this form only when no wave has a second tile and the grid fills at least four
     //  fifths of the CUs; a wave without a tile only joins the barrier.)
     constexpr bool CUWIDE = WPB == 16;
-    if (!ENTRY_FIRST && CUWIDE && (int64_t)blockIdx.x * WPB + wave >= nfull) __syncthreads();
-    for (int64_t t = (int64_t)blockIdx.x * WPB + wave; t < nfull; t += (int64_t)ngrid * WPB) {
+    // ENTRY_FIRST: ONE tile per wave (the launcher's grid is ceil(nfull / 16) workgroups, at most one per CU), so
+    // the tile index and the tile count fit 32 bits: index and compare stay on the scalar unit, and the body
+    // leaves after its one pass.
+    const int64_t t_first = ENTRY_FIRST ? (int64_t)(blockIdx.x * (unsigned)WPB + (unsigned)wave)
+                                        : (int64_t)blockIdx.x * WPB + wave;
+    const bool has_tile = ENTRY_FIRST ? (unsigned)t_first < (unsigned)nfull : t_first < nfull;
+    if (!ENTRY_FIRST && CUWIDE && !has_tile) __syncthreads();
+    for (int64_t t = t_first; ENTRY_FIRST ? has_tile : t < nfull; t += (int64_t)ngrid * WPB) {
         const int64_t row_base = t * R;
         // ---- A
-        const char *src = reinterpret_cast<const char *>(logits + row_base * C);
+        // (ENTRY_FIRST: 32-bit tile index, C > 0 -- one 32 x 32 -> 64-bit product on the scalar unit)
+        const char *src = ENTRY_FIRST
+            ? reinterpret_cast<const char *>(logits) + (uint64_t)((unsigned)t * (unsigned)R) * (unsigned)C * sizeof(T)
+            : reinterpret_cast<const char *>(logits + row_base * C);
         // label and index first (they return ahead of the tile: loads return in order), the tile's
         // NI chunks per lane behind them
         int64_t y64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(labels + row_base) + sub8);
@@ -513,29 +541,45 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
             stamps[9] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));    // HW_REG_XCC_ID
         }
 #endif
-        // ENTRY_FIRST: the arguments past the preloaded ones that the loop uses (and the grid size, which the runtime
-        // appends to them) pass through here: the compiler asks for them in one burst and waits once, at this
-        // point of the program.  (No instruction.)
+        // ENTRY_FIRST: the arguments past the preloaded ones that the body uses pass through here: the compiler asks
+        // for them in one burst and waits once, at this point of the program.  (No instruction.)
         if constexpr (ENTRY_FIRST)
-            asm volatile("" : "+s"(residuals), "+s"(inv_scale), "+s"(grad_scale), "+s"(grad), "+s"(gen_ticks), "+s"(ngrid));
+            asm volatile("" : "+s"(residuals), "+s"(inv_scale), "+s"(grad_scale), "+s"(grad), "+s"(gen_ticks));
         if (CUWIDE) {
             __builtin_amdgcn_sched_barrier(0);       // (the loads are issued, THEN the barrier)
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
         }
+        // ENTRY_FIRST: the lane's LDS geometry, while the tile is in flight.  (The asm is empty: it only makes what
+        // is derived from the lane, the wave and C depend on this point of the program.)
+        if constexpr (ENTRY_FIRST) {
+            asm volatile("" : "+v"(lane_l), "+s"(wave_l), "+s"(C_l));
+            g_l = lane_l & (G - 1);
+            sub_l = (int)((unsigned)lane_l / G);
+            nv_l = C_l / V;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {                      // (as in front of the loop, from the copies)
+                const int vec = k * G + g_l;
+                live[k] = (EXACT && k < KMAX - 1) || vec < nv_l;
+                slot_off[k] = (sub_l * C_l + (live[k] ? vec : nv_l - 1) * V) * (int)sizeof(T);
+            }
+            row_off = sub_l * C_l * (int)sizeof(T);
+            wtile_l = smem + (size_t)wave_l * WTILE;
+        }
+        if constexpr (ENTRY_FIRST) tile16 = reinterpret_cast<vu4 *>(wtile_l);
         if (ENTRY_FIRST && !have_gain) {             // (wave-uniform; behind the barrier)
             gscale = grad_gain(inv_scale, grad_scale);
             have_gain = true;
         }
         bool okrow = true;
-        ix = idx != nullptr ? ix : row_base + sub;
-        if (y64 < 0 || y64 >= C) { y64 = 0; okrow = false; }
+        ix = idx != nullptr ? ix : row_base + sub_l;
+        if (y64 < 0 || y64 >= C_l) { y64 = 0; okrow = false; }
         if (ix < 0 || ix >= N) { ix = 0; okrow = false; }
         // the tile first, the gather once it has landed: 64 K random 4-byte reads queued beside the
         // streaming reads cost the launch 1 us (12.0 against 11.0 us at 65 536 x 100); issued here they
         // are L2 hits on a quiet queue and fly during the first half of phase B
 #pragma unroll
-        for (int i = 0; i < NI; ++i) tile16[i * WAVE + lane] = stg[i];
+        for (int i = 0; i < NI; ++i) tile16[i * WAVE + lane_l] = stg[i];
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(y64), "+v"(ix) : : "memory");
         float pi = weights != nullptr ? weights[ix] : 1.0f;
         RLVI_STAMP(2);
@@ -544,7 +588,7 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
 
         // ---- B
         const int y = (int)y64;
-        char *zrow = wtile + row_off;
+        char *zrow = wtile_l + row_off;
         float zy;
         {
             float tt[1];
@@ -553,7 +597,7 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
         }
         float v[KMAX][V];
 #pragma unroll
-        for (int k = 0; k < KMAX; ++k) VecIO<T, V>::load(reinterpret_cast<T *>(wtile + slot_off[k]), v[k]);
+        for (int k = 0; k < KMAX; ++k) VecIO<T, V>::load(reinterpret_cast<T *>(wtile_l + slot_off[k]), v[k]);
         float m = v[0][0];
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
@@ -591,8 +635,8 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
             for (int k = 0; k < KMAX; ++k) {
                 float z[V];
                 asm volatile("" ::: "memory");                     // re-read, do not keep the first copy live
-                VecIO<T, V>::load(reinterpret_cast<T *>(wtile + slot_off[k]), z);
-                const int col = (k * G + g) * V;
+                VecIO<T, V>::load(reinterpret_cast<T *>(wtile_l + slot_off[k]), z);
+                const int col = (k * G + g_l) * V;
 #pragma unroll
                 for (int j = 0; j < V; ++j) earlier += (live[k] && z[j] == m && col + j < y) ? 1 : 0;
             }
@@ -609,11 +653,11 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
                 for (int j = 0; j < V; ++j) {
                     o[j] = v[k][j] * inv_s;
                     if (sizeof(T) != 4) {
-                        const int colc = (live[k] ? (k * G + g) : nv - 1) * V + j;
+                        const int colc = (live[k] ? (k * G + g_l) : nv_l - 1) * V + j;
                         if (colc == y) o[j] -= gs;
                     }
                 }
-                VecIO<T, V>::store(reinterpret_cast<T *>(wtile + slot_off[k]), o);   // in place
+                VecIO<T, V>::store(reinterpret_cast<T *>(wtile_l + slot_off[k]), o);   // in place
             }
             if (sizeof(T) == 4) {
                 // -onehot term: one read-modify-write of the label entry, ordered behind this wave's
@@ -625,7 +669,7 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
                 zf[y] = fmaf(-gscale, pi, zf[y]);
             }
         }
-        if (g == 0 && okrow && residuals != nullptr) residuals[ix] = li;
+        if (g_l == 0 && okrow && residuals != nullptr) residuals[ix] = li;
         acc += okrow ? weighted_nll(li, pi) : 0.0f;
         hits += (hit && okrow) ? 1.0f : 0.0f;
         __builtin_amdgcn_wave_barrier();
@@ -641,7 +685,7 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
             char *gdst = reinterpret_cast<char *>(grad + row_base * C);
             vu4 st[NI];
 #pragma unroll
-            for (int i = 0; i < NI; ++i) st[i] = tile16[i * WAVE + lane];      // inside this wave's slice
+            for (int i = 0; i < NI; ++i) st[i] = tile16[i * WAVE + lane_l];    // inside this wave's slice
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 if (EXACT16 && i < NI - 1) {
@@ -660,14 +704,15 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
         RLVI_STAMP(7);
         first_tile = false;
 #endif
+        if constexpr (ENTRY_FIRST) break;
     }
 
     // (ENTRY_FIRST: a wave without a tile joins the barrier of its workgroup's one generation of tiles here, behind
     //  the loop it did not enter, so that its wait for the barrier is not the first thing in the kernel)
-    if (ENTRY_FIRST && (int64_t)blockIdx.x * WPB + wave >= nfull) __syncthreads();
+    if (ENTRY_FIRST && !has_tile) __syncthreads();
     // every lane of a row's group carried the row's sums: count each row once
-    double a = wave_sum((double)(g == 0 ? acc : 0.0f));
-    double h = wave_sum((double)(g == 0 ? hits : 0.0f));
+    double a = wave_sum((double)(g_l == 0 ? acc : 0.0f));
+    double h = wave_sum((double)(g_l == 0 ? hits : 0.0f));
     __shared__ double sh[2 * WPB];
     if (lane == 0) { sh[2 * wave] = a; sh[2 * wave + 1] = h; }
     if (bad) atomicOr(status, RLVI_ST_RANGE);
@@ -927,6 +972,8 @@ struct MstepCall {
 template <typename T, int V, int G, int KMAX, int WPB>
 static int launch_wave(const MstepCall<T> &c, bool exact, int64_t nb, int64_t nfull, int hold_ticks, int gen_ticks) {
     constexpr size_t LDS = (size_t)WPB * ((KMAX * V * sizeof(T) + 15) / 16) * 1024;
+    // (the kernel's ENTRY_FIRST form does not stride: a grid that left a wave a second tile would drop it)
+    if (WPB == 16 && sizeof(T) == 4 && nfull > nb * WPB) return RLVI_E_LIMIT;
     auto go = [&](auto kern) {
         if constexpr (WPB == 16) {      // (> 64 KiB of dynamic LDS)
             if (const int e = allow_dyn_lds(kern, LDS)) return e;
@@ -1007,6 +1054,8 @@ static int launch_mstep(const MstepCall<T> &c) {
         cuwide = c.knobs.cuwide && c.grad != nullptr && hold_ticks == 0 && nb16 <= c.cus &&
                  nb16 * 5 >= (int64_t)c.cus * 4 && nb16 <= MSTEP_MAX_BLOCKS;
         if (cuwide) {
+            // (nb16 workgroups of 16 waves = ONE tile per wave, never a capped grid: the fp32 kernel of this form
+            //  relies on it -- 32-bit tile index, one pass through its body, no stride)
             nb = nb16;
             ws_note_mstep(c.ws, 3);
             rc = launch_wave<T, V, G, KMAX, WPB16>(c, exact, nb, nfull, 0, 0);

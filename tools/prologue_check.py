@@ -8,6 +8,10 @@ rlvi_amd/_build.py and reports per kernel:
   preload   .amdhsa_user_sgpr_kernarg_preload_length: SGPRs of kernel arguments that arrive with the wave
   instr     instructions from the entry to the first global_load (behind the compatibility header that
             fetches the preloaded arguments the old way on firmware that does not preload)
+  last      instructions from the entry to the LAST global_load of the first burst, and the burst's size: the loads
+            up to the first s_barrier, s_waitcnt vmcnt(..) or branch behind the first one.  For the M-step's bench
+            kernel that is label, index and the seven tile pieces; a SIMD's last wave asks for its tile only when
+            every wave in front of it has issued this many instructions
   waits     s_waitcnt lgkmcnt(..) in that stretch -- each one a stall on the argument block or on a scalar load
   rcp       whether a v_rcp_f32 (the software integer division) occurs in it
   state     E-step only: the slice loads (the first global_load) are issued before ANY scalar load that does not go
@@ -82,6 +86,13 @@ def analyse(asm):
             ins = ins[k + 1:]
         first = next((i for i, (op, _) in enumerate(ins) if op.startswith("global_load")), len(ins))
         head = ins[:first]
+        last, burst = first, 0
+        for i in range(first, len(ins)):
+            op, a = ins[i]
+            if op == "s_barrier" or op.startswith("s_cbranch") or op == "s_branch" or (op == "s_waitcnt" and "vmcnt" in a):
+                break
+            if op.startswith("global_load"):
+                last, burst = i, burst + 1
         waits = sum(1 for op, a in head if op == "s_waitcnt" and "lgkmcnt" in a)
         rcp = any(op.startswith("v_rcp_f32") for op, _ in head)
         # kernarg pointer: s[0:1] without preload, s[0:1] as well with it (the preloaded SGPRs follow it)
@@ -98,7 +109,7 @@ def analyse(asm):
         s = sets.get(name, {})
         vg, ag = s.get("num_vgpr", 0), s.get("num_agpr", 0)
         alloc = max((vg + ag + 7) // 8 * 8, 8)
-        rows[name] = dict(preload=preload, instr=first, waits=waits, rcp=rcp, state=state, stamp_first=stamp_first,
+        rows[name] = dict(preload=preload, instr=first, last=last, burst=burst, waits=waits, rcp=rcp, state=state, stamp_first=stamp_first,
                           vgpr=vg + ag,
                           sgpr=int(d.get("next_free_sgpr", s.get("numbered_sgpr", 0))),
                           scratch=s.get("private_seg_size", int(d.get("private_segment_fixed_size", 0))),
@@ -111,7 +122,7 @@ def fmt(r):
     if r is None:
         return "(no such kernel)"
     st = "-" if r["state"] is None else ("yes" if r["state"] else "NO")
-    return (f"preload {r['preload']:2d}  instr {r['instr']:4d}  waits {r['waits']}  rcp {'YES' if r['rcp'] else 'no':3s}  "
+    return (f"preload {r['preload']:2d}  instr {r['instr']:4d}  last {r['last']:4d} ({r['burst']} loads)  waits {r['waits']}  rcp {'YES' if r['rcp'] else 'no':3s}  "
             f"state {st:3s}  vgpr {r['vgpr']:3d} sgpr {r['sgpr']:3d} scratch {r['scratch']} lds {r['lds']:5d} waves {r['waves']}")
 
 
