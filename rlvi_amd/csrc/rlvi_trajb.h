@@ -617,28 +617,37 @@ __device__ __forceinline__ TbSolved trajb_solve(
                 }
             }
             __syncthreads();
+            // (the reducer's combine on the stamps' axis, first round of workgroup 0: dbg[982] behind the barrier,
+            //  dbg[989] at the publish store)
+            if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) dbg[982] = wall_clock64();
             if (wave == 0 && !dead && sh.out.dead == 0) {
-                double tS = 0.0, tP = 0.0, tQ = 0.0, tD = 0.0, tM = (double)__builtin_inff();
-                double t3 = 0.0, t4 = 0.0;
+                // lane l stores granule l & 7 of replica l >> 3: one store per lane -- so it combines quantity
+                // l & 7 alone: the gathering waves' four partials in wave order from 0.0 (from +inf and by `<` for
+                // the minimum), one conversion.  (Written as seven sums and a select chain it compiled to seven
+                // divergent branches, one per quantity, each with its own LDS round trip: 117 instructions and
+                // 0.48 us of a lone wave on the path of ALL workgroups' totals; this form is 53 and 0.16 us.)
+                static_assert(XCHG3B_REPLICAS * 8 == WAVE && TB_NV <= 8, "one granule of one replica per lane");
+                // (the lane as formed here, in every round: hoisted out of the round loop, the slot addresses and
+                //  selects made of it would hold registers across the sums)
+                int cl = lane;
+                asm volatile("" : "+v"(cl));
+                const int gq = cl & 7;
+                const bool is_min = gq == 4;
+                const int rq = gq < 7 ? gq : 6;              // (granule 7 is no quantity: never stored)
+                double tot = is_min ? (double)__builtin_inff() : 0.0;
 #pragma unroll
                 for (int w = 0; w < TB_PER; ++w) {            // fixed order
-                    tS += sh.red[w][0]; tP += sh.red[w][1]; tQ += sh.red[w][2]; tD += sh.red[w][3];
-                    tM = sh.red[w][4] < tM ? sh.red[w][4] : tM;
-                    t3 += sh.red[w][5]; t4 += sh.red[w][6];
+                    const double x = sh.red[w][rq];
+                    tot = is_min ? (x < tot ? x : tot) : tot + x;
                 }
-                // lane l stores granule l & 7 of replica l >> 3: one store per lane
-                static_assert(XCHG3B_REPLICAS * 8 == WAVE && TB_NV <= 8, "one granule of one replica per lane");
-                const int gq = lane & 7;
-                float val = gq == 0 ? (float)tS : gq == 1 ? (float)tP : gq == 2 ? (float)tQ
-                            : gq == 3 ? (float)tD : gq == 4 ? (float)tM : gq == 5 ? (float)t3
-                            : (float)t4;
+                float val = (float)tot;
                 bool xdead = false;
                 if (pt != nullptr) {
-                    // lane = (rank r = lane >> 3, granule gq): one system-scope store into rank r's inbox
+                    // lane = (rank r = cl >> 3, granule gq): one system-scope store into rank r's inbox
                     // slot [round parity][node b][this rank], then this rank's own slots [..][rank r]
                     // until every rank's granules carry this round's tag; totals in rank order (the same
                     // tree on every rank: identical bits everywhere)
-                    const int r = lane >> 3;
+                    const int r = cl >> 3;
                     const bool mine = r < pworld && gq < nq;
                     const size_t slot = ((size_t)(ptag & 1u) * TJ_MAXK + b) * MAX_PEERS;
                     if (mine) {
@@ -669,8 +678,12 @@ __device__ __forceinline__ TbSolved trajb_solve(
                     }
                     val = (float)acc;
                 }
+                if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) {
+                    asm volatile("" : "+v"(val));          // (the stamp is taken with the granule in hand)
+                    dbg[989] = wall_clock64();
+                }
                 if (gq < nq && !xdead)
-                    __hip_atomic_store(B + ((size_t)(lane >> 3) * TJ_MAXK + b) * XCHG3_GRANULES + gq,
+                    __hip_atomic_store(B + ((size_t)(cl >> 3) * TJ_MAXK + b) * XCHG3_GRANULES + gq,
                                        ((unsigned long long)tag << 32) | __float_as_uint(val),
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }

@@ -175,6 +175,9 @@ with torch.cuda.stream(side):
             hs = full[996:999].astype(np.int64)
             print("   helper wave [start, done] and the recurrence wave past its second barrier, us on the same axis:",
                   [round(float(v - cs[0]) / 100.0, 2) for v in hs])
+        if int(full[982]) > 0 and int(full[989]) > 0:
+            print(f"reducer of node 0: behind its barrier at {(int(full[982]) - int(st[0])) / 100.0:.2f}, granule in hand at "
+                  f"{(int(full[989]) - int(st[0])) / 100.0:.2f} us since kernel start: combine {(int(full[989]) - int(full[982])) / 100.0:.2f} us")
         # the kernel's entry on the stamps' axis: stamped as its first instruction (986 entry, 987 first data loads
         # issued, 988 slice landed); a build without these has the kernel's length from its entry (961), taken at the
         # last stamp, and its first two stamps sit behind the issue of the slice loads and behind their arrival
