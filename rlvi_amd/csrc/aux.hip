@@ -313,8 +313,7 @@ extern "C" int rlvi_logistic_nll_f64(const double *X, const double *w, double b,
 // M-step's bytes (logits in, gradient out), timed in the same rotation and graph as the M-step itself.
 // ---------------------------------------------------------------------------------------
 namespace rlvi {
-typedef unsigned int aux_vu4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void stream_copy_kernel(aux_vu4 *__restrict__ dst, const aux_vu4 *__restrict__ src,
+__global__ __launch_bounds__(256) void stream_copy_kernel(vu4 *__restrict__ dst, const vu4 *__restrict__ src,
                                                           int64_t n16) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride)
@@ -331,5 +330,5 @@ extern "C" int rlvi_stream_copy(void *dst, const void *src, size_t bytes, void *
     const int64_t cap = (int64_t)device_info().cus * 4 * 4;     // 16 waves per CU
     if (nb > cap) nb = cap;
     return launch(stream_copy_kernel, dim3((unsigned)nb), dim3(256), 0, static_cast<hipStream_t>(stream),
-                  static_cast<aux_vu4 *>(dst), static_cast<const aux_vu4 *>(src), n16);
+                  static_cast<vu4 *>(dst), static_cast<const vu4 *>(src), n16);
 }

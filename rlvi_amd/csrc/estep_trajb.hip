@@ -22,9 +22,8 @@
 //     8 replicas and a workgroup polls replica blockIdx % 8 (2.4-2.9 -> 0.8 us for that hop).
 // Pads have e = 0 and drop out of every sum.  Per-thread and per-wave sums are fp32; cross-wave and
 // cross-workgroup sums of S are fp64, in a fixed order, so every workgroup sees bit-identical totals
-// and identical inputs + workspace state give identical bits.  Protocol (sc1 stores / loads,
-// self-tagged granules, parity buffers, tags from the workspace base, wall-clock-bounded spins) as in
-// rlvi_coop.h.
+// and identical inputs + workspace state give identical bits.  Granules, records, bounded waits and tags: the
+// exchange layer of rlvi_coop.h.
 #include "rlvi_trajb.h"
 
 namespace rlvi {

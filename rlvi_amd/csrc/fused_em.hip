@@ -28,8 +28,6 @@
 
 namespace rlvi {
 
-typedef unsigned int fe_vu4 __attribute__((ext_vector_type(4)));
-
 constexpr int FE_WAVES = 8;                      // waves per workgroup
 constexpr int FE_THREADS = FE_WAVES * WAVE;
 constexpr int FE_TPW = 2;                        // tiles per wave
@@ -89,8 +87,7 @@ __device__ __forceinline__ void fe_batch_scalars(float acc, float hits, const Tb
         const unsigned long long bits = (unsigned long long)__double_as_longlong(
             (tid >> 1) == 0 ? rec[0] : (tid >> 1) == 1 ? rec[1] : (tid >> 1) == 2 ? rec[2] : rec[3]);
         const uint32_t half = (tid & 1) ? (uint32_t)(bits >> 32) : (uint32_t)bits;
-        __hip_atomic_store(frec + (size_t)b * 8 + tid, ((unsigned long long)ftag << 32) | half,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        publish(frec + (size_t)b * 8 + tid, ftag, half);
     }
     if (b != 0) return;
     if (tid == 0) fin_dead = 0;
@@ -98,33 +95,20 @@ __device__ __forceinline__ void fe_batch_scalars(float acc, float hits, const Tb
     double t[PART_STRIDE] = {0.0, 0.0, 0.0, 0.0};
     if (wave < (G + WAVE - 1) / WAVE) {
         const bool mine = tid < G;
-        const unsigned long long pa = (unsigned long long)(uintptr_t)(frec + (size_t)(mine ? tid : 0) * 8);
+        const gu64 *p = frec + (size_t)(mine ? tid : 0) * 8;
         const unsigned long long t0 = wall_clock64();
-        const unsigned long long spin_ticks = spin_bound(hdr);
-        fe_vu4 r0, r1, r2, r3;
-        bool timeout = false;
-        for (unsigned spin = 0;; ++spin) {
-            asm volatile(
-                "global_load_dwordx4 %0, %4, off sc1\n\t"
-                "global_load_dwordx4 %1, %4, off offset:16 sc1\n\t"
-                "global_load_dwordx4 %2, %4, off offset:32 sc1\n\t"
-                "global_load_dwordx4 %3, %4, off offset:48 sc1\n\t"
-                "s_waitcnt vmcnt(0)"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-                : "v"(pa)
-                : "memory");
-            const bool ok = !mine || (r0.y == ftag && r0.w == ftag && r1.y == ftag && r1.w == ftag &&
-                                      r2.y == ftag && r2.w == ftag && r3.y == ftag && r3.w == ftag);
-            if (__all(ok)) break;
-            if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-        }
+        vu4 r[PART_STRIDE];
+        const bool timeout = !bounded_wait(t0, spin_bound(hdr), [&] {
+            rec_load<4>(p, r);
+            const bool ok = !mine || rec_tagged<8>(r, ftag);
+            return __all(ok) != 0;
+        });
         if (timeout) {
             if (lane == 0) { atomicOr(&hdr->status, RLVI_ST_TIMEOUT); fin_dead = 1; }
         } else if (mine) {
-            t[0] = __longlong_as_double((long long)(((unsigned long long)r0.z << 32) | r0.x));
-            t[1] = __longlong_as_double((long long)(((unsigned long long)r1.z << 32) | r1.x));
-            t[2] = __longlong_as_double((long long)(((unsigned long long)r2.z << 32) | r2.x));
-            t[3] = __longlong_as_double((long long)(((unsigned long long)r3.z << 32) | r3.x));
+#pragma unroll
+            for (int c = 0; c < PART_STRIDE; ++c)
+                t[c] = __longlong_as_double((long long)(((unsigned long long)r[c].z << 32) | r[c].x));
         }
     }
 #pragma unroll
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
     const TbWarm wm = tb_warm(ws, B, K);
     bool tile_ok[FE_TPW];
     int64_t y64[FE_TPW];
-    fe_vu4 stg[FE_TPW][NI];
+    vu4 stg[FE_TPW][NI];
 #pragma unroll
     for (int j = 0; j < FE_TPW; ++j) {
         const int64_t r0 = wrow0 + (int64_t)j * FE_R;
@@ -214,7 +198,7 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
             const char *src = reinterpret_cast<const char *>(logits + r0 * C);
 #pragma unroll
             for (int i = 0; i < NI; ++i)
-                stg[j][i] = __builtin_nontemporal_load(reinterpret_cast<const fe_vu4 *>(src + dma_off[i]));
+                stg[j][i] = __builtin_nontemporal_load(reinterpret_cast<const vu4 *>(src + dma_off[i]));
         }
     }
     FE_STAMP(1);   // loads issued
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
         char *wtile = wbase + j * WTILE;
         {
             // (tile j only: loads return in order, so tile 0 is worked on while tile 1 is in flight)
-            fe_vu4 *t16 = reinterpret_cast<fe_vu4 *>(wtile);
+            vu4 *t16 = reinterpret_cast<vu4 *>(wtile);
 #pragma unroll
             for (int i = 0; i < NI; ++i) t16[i * WAVE + lane] = stg[j][i];
         }
@@ -345,20 +329,20 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
 #pragma unroll
         for (int j = 0; j < FE_TPW; ++j) {
             if (!tile_ok[j]) continue;
-            const fe_vu4 *t16 = reinterpret_cast<const fe_vu4 *>(wbase + j * WTILE);
+            const vu4 *t16 = reinterpret_cast<const vu4 *>(wbase + j * WTILE);
             char *gdst = reinterpret_cast<char *>(grad + (wrow0 + (int64_t)j * FE_R) * C);
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
-                const fe_vu4 raw = t16[dma_off[i] >> 4];
+                const vu4 raw = t16[dma_off[i] >> 4];
                 const FeRow ri = rowinfo[wave][j][rowc[i]];
                 const int d = ri.y - colc[i];
-                fe_vu4 o;
+                vu4 o;
                 o.x = __float_as_uint(fe_grad(__uint_as_float(raw.x), ri.inv_s, d == 0, ri.pw, inv_scale));
                 o.y = __float_as_uint(fe_grad(__uint_as_float(raw.y), ri.inv_s, d == 1, ri.pw, inv_scale));
                 o.z = __float_as_uint(fe_grad(__uint_as_float(raw.z), ri.inv_s, d == 2, ri.pw, inv_scale));
                 o.w = __float_as_uint(fe_grad(__uint_as_float(raw.w), ri.inv_s, d == 3, ri.pw, inv_scale));
                 if ((EXACT && i < NI - 1) || i * WAVE + lane < nchunk)
-                    __builtin_nontemporal_store(o, reinterpret_cast<fe_vu4 *>(gdst + dma_off[i]));
+                    __builtin_nontemporal_store(o, reinterpret_cast<vu4 *>(gdst + dma_off[i]));
             }
         }
     }

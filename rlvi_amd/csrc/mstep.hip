@@ -19,8 +19,6 @@
 
 namespace rlvi {
 
-typedef unsigned int vu4 __attribute__((ext_vector_type(4)));
-
 constexpr int MSTEP_THREADS = 256;
 constexpr int MSTEP_WAVES = MSTEP_THREADS / WAVE;
 

@@ -91,18 +91,14 @@ constexpr int XCHG_GRANULES = 4;                                        // per w
 // pollers on the same lines serialise at the memory side
 constexpr int XCHG_REPLICAS = 8;
 constexpr size_t WS_XCHG_BYTES = 2ull * XCHG_REPLICAS * MAX_COOP_WG * XCHG_GRANULES * 8; // 128 KiB
-// second exchange region: 8-granule records (three doubles) of the trajectory E-step
-constexpr int XCHG2_GRANULES = 8;
-constexpr size_t WS_XCHG2_OFF = WS_XCHG_OFF + WS_XCHG_BYTES;
-constexpr size_t WS_XCHG2_BYTES = 2ull * MAX_COOP_WG * XCHG2_GRANULES * 8;     // 32 KiB
 // warm-start state of the trajectory E-step: {int64 n, int32 k, int32 pad, float nodes[64]}
-constexpr size_t WS_TRAJ_OFF = WS_XCHG2_OFF + WS_XCHG2_BYTES;
+constexpr size_t WS_TRAJ_OFF = WS_XCHG_OFF + WS_XCHG_BYTES;
 constexpr size_t WS_TRAJ_BYTES = 512;
 constexpr size_t WS_PART_OFF = WS_TRAJ_OFF + WS_TRAJ_BYTES;
 constexpr int MSTEP_MAX_BLOCKS = 1024;   // partial records (and so workgroups) of one M-step launch
 constexpr int PART_STRIDE = 4;   // per block: {sum pi*l * inv_scale, hits*100/B, sum pi*l, hits}
 constexpr size_t WS_PART_BYTES = (size_t)MSTEP_MAX_BLOCKS * PART_STRIDE * 8;
-// third exchange region (trajectory E-step, estep_trajb.hip), 64-byte records of eight self-tagged
+// second exchange region (trajectory E-step, estep_trajb.hip), 64-byte records of eight self-tagged
 // fp32 granules {S, P, Q, D, min, R3, R4, -}: stage A [2 parities][64 nodes][256 workgroups], stage B [2][64 nodes]
 constexpr int XCHG3_GRANULES = 8;
 // a second set of records for calls WITH `out` (their own finalize launch reduces and clears them): such a call may
@@ -113,7 +109,7 @@ constexpr size_t WS_XCHG3A_BYTES = 2ull * 64 * MAX_COOP_WG * XCHG3_GRANULES * 8;
 constexpr size_t WS_XCHG3B_OFF = WS_XCHG3A_OFF + WS_XCHG3A_BYTES;
 constexpr int XCHG3B_REPLICAS = 8;     // the per-node totals are published in 8 copies (one per 32 pollers)
 constexpr size_t WS_XCHG3B_BYTES = 2ull * XCHG3B_REPLICAS * 64 * XCHG3_GRANULES * 8;   // 64 KiB
-// fourth exchange region (radix-descent threshold, threshold.hip): 32-byte records of four self-tagged
+// third exchange region (radix-descent threshold, threshold.hip): 32-byte records of four self-tagged
 // granules {count, min key, sum lo, sum hi}; a workgroup publishes up to 2 x 256 of them per exchange
 // (this digit's bins and, speculatively, the next digit's): stage A [2 parities][256 workgroups][512
 // records], stage B (the totals) [2][8 replicas][512 records]
@@ -358,6 +354,7 @@ struct Half<f16_t> {                                              // fp16
 };
 
 typedef float vf4 __attribute__((ext_vector_type(4)));
+typedef unsigned int vu4 __attribute__((ext_vector_type(4)));     // 16 bytes: a tile piece, two exchange granules
 
 // V consecutive elements of T <-> fp32: fp32 vectors of 1, 2 or 4, 2-byte vectors (bf16, fp16) of 1, 2, 4 or 8
 // elements, widened and narrowed through Half<T>.  V elements must be V * sizeof(T)-byte aligned (vec_fits).

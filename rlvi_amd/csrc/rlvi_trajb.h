@@ -12,8 +12,6 @@
 
 namespace rlvi {
 
-typedef unsigned int tb_vu4 __attribute__((ext_vector_type(4)));
-
 // Workgroup size: 256 threads = one wave per SIMD (the per-wave butterflies are a fixed cost per
 // wave and chunk, so fewer, fatter waves win as long as the slice fits the registers); the main loop
 // has no memory operations to hide and eight independent nodes of instruction-level parallelism.
@@ -81,57 +79,25 @@ __device__ __forceinline__ float wave_reduce8(const float (&v)[TB_CHUNK]) {
     return group_allreduce<8>(x, FAdd());
 }
 
-// 48-byte record = six granules {tag32 | payload32}: {S, P, Q, D, min, -}; the first nq (4 or 5)
-// must carry `tag`.  Each 8-byte granule is self-tagged, so it does not matter that a 16-byte load
-// is only granule-atomic.
+// A record of up to eight fp32 granules {S, P, Q, D, min, R3, R4, -} (rlvi_coop.h); the first nq carry this
+// step's tag: 4 {S, P, Q, D}, 5 {.., min} or 7 {.., R3, R4}.
 __device__ __forceinline__ bool load_rec(gu64 *p, uint32_t tag, int nq, float (&val)[TB_NV]) {
-    // nq granules of the record carry this step's tag: 4 {S, P, Q, D}, 5 {.., min} or 7 {.., R3, R4}
-    tb_vu4 q0, q1, q2, q3;
-    q2.x = 0u; q2.y = tag; q2.z = 0u; q2.w = tag;
-    q3.x = 0u; q3.y = tag; q3.z = 0u; q3.w = tag;
+    // what is not loaded, or is no part of the record, reads as {0, tag}: ONE chain of eight tag compares behind
+    // whichever load ran (a chain of its own per load: 0.1 us per E-step at the bench size, two waits per round)
+    vu4 q[4];
+    q[2] = q[3] = granule_pair(tag, 0u, 0u);
     if (nq > 5) {
-        asm volatile(
-            "global_load_dwordx4 %0, %4, off sc1\n\t"
-            "global_load_dwordx4 %1, %4, off offset:16 sc1\n\t"
-            "global_load_dwordx4 %2, %4, off offset:32 sc1\n\t"
-            "global_load_dwordx4 %3, %4, off offset:48 sc1\n\t"
-            "s_waitcnt vmcnt(0)"
-            : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
-            : "v"((unsigned long long)(uintptr_t)p)
-            : "memory");
-        q3.w = tag;                      // (granule 7 is not part of a 7-granule record)
+        rec_load<4>(p, q);
+        q[3].w = tag;
     } else if (nq > 4) {
-        asm volatile(
-            "global_load_dwordx4 %0, %3, off sc1\n\t"
-            "global_load_dwordx4 %1, %3, off offset:16 sc1\n\t"
-            "global_load_dwordx4 %2, %3, off offset:32 sc1\n\t"
-            "s_waitcnt vmcnt(0)"
-            : "=&v"(q0), "=&v"(q1), "=&v"(q2)
-            : "v"((unsigned long long)(uintptr_t)p)
-            : "memory");
-        q2.w = tag;                      // (granule 5 is not part of a 5-granule record)
-    } else
-        asm volatile(
-            "global_load_dwordx4 %0, %2, off sc1\n\t"
-            "global_load_dwordx4 %1, %2, off offset:16 sc1\n\t"
-            "s_waitcnt vmcnt(0)"
-            : "=&v"(q0), "=&v"(q1)
-            : "v"((unsigned long long)(uintptr_t)p)
-            : "memory");
-    val[0] = __uint_as_float(q0.x); val[1] = __uint_as_float(q0.z);
-    val[2] = __uint_as_float(q1.x); val[3] = __uint_as_float(q1.z);
-    val[4] = __uint_as_float(q2.x); val[5] = __uint_as_float(q2.z);
-    val[6] = __uint_as_float(q3.x); val[7] = __uint_as_float(q3.z);
-    return q0.y == tag && q0.w == tag && q1.y == tag && q1.w == tag && q2.y == tag && q2.w == tag &&
-           q3.y == tag && q3.w == tag;
-}
-
-__device__ __forceinline__ void store_rec(gu64 *p, uint32_t tag, int nq, const float (&val)[TB_NV]) {
+        rec_load<3>(p, q);
+        q[2].w = tag;
+    } else {
+        rec_load<2>(p, q);
+    }
 #pragma unroll
-    for (int q = 0; q < TB_NV; ++q)
-        if (q < nq)
-            __hip_atomic_store(p + q, ((unsigned long long)tag << 32) | __float_as_uint(val[q]),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int g = 0; g < TB_NV; ++g) val[g] = __uint_as_float((g & 1) ? q[g >> 1].z : q[g >> 1].x);
+    return rec_tagged<8>(q, tag);
 }
 
 // warm-start state of the previous call
@@ -251,11 +217,8 @@ __device__ __forceinline__ TbSolved trajb_solve(
     gu64 *bufA = (gu64 *)(reinterpret_cast<unsigned long long *>(wsb + WS_XCHG3A_OFF));
     gu64 *bufB = (gu64 *)(reinterpret_cast<unsigned long long *>(wsb + WS_XCHG3B_OFF));
     TrajState *state = reinterpret_cast<TrajState *>(wsb + (pt != nullptr ? WS_PEER_STATE_OFF : WS_TRAJ_OFF));
-    uint32_t tag = __hip_atomic_load((gu32 *)&hdr->epoch_base, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    // (sharded over several GPUs: a peer may legitimately be late -- another process, another stream --,
-    //  and every wait downstream of the cross-rank hop inherits its lateness: 100 x the bound)
-    const unsigned long long spin_ticks = spin_bound(hdr) * (pt != nullptr ? 100ull : 1ull);
+    uint32_t tag = first_tag(hdr);
+    const unsigned long long spin_ticks = spin_bound(hdr, pt != nullptr);
     int xstep = 0;
     bool dead = false;
     // sharded over several GPUs (pt != nullptr): N is the population over ALL ranks; the reducer of a
@@ -519,9 +482,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
                     if (node < n1 && j < nq && !dead) {
                         const float v = j == 0 ? tI : j == 1 ? tP : j == 2 ? tQ : j == 3 ? tD : j == 4 ? wmin_all
                                         : j == 5 ? t3 : t4;
-                        __hip_atomic_store(A + ((size_t)node * MAX_COOP_WG + b) * XCHG3_GRANULES + j,
-                                           ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
+                        publish(A + ((size_t)node * MAX_COOP_WG + b) * XCHG3_GRANULES + j, tag, __float_as_uint(v));
                     }
                 }
             }
@@ -556,23 +517,20 @@ __device__ __forceinline__ TbSolved trajb_solve(
 #pragma unroll
             for (int w = 0; w < TB_NW; ++w) dq += (double)sh.wp[w][lane][wave];
             gu64 *rec = A + ((size_t)lane * MAX_COOP_WG + b) * XCHG3_GRANULES;
-            __hip_atomic_store(rec + wave, ((unsigned long long)tag << 32) | __float_as_uint((float)dq),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            publish(rec + wave, tag, __float_as_uint((float)dq));
             // second store of a lane: wave 3 the minimum (granule 4), waves 0 and 1 R3 and R4 (granules 5, 6)
             if (wave == 3 && nq > 4) {
                 float wmin = sh.pmin[0];
 #pragma unroll
                 for (int w = 1; w < TB_NW; ++w) wmin = fminf(wmin, sh.pmin[w]);
-                __hip_atomic_store(rec + 4, ((unsigned long long)tag << 32) | __float_as_uint(wmin),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                publish(rec + 4, tag, __float_as_uint(wmin));
                 if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && round == 0 && lane == 0) dbg[898] = __float_as_uint(wmin);
             }
             if (wave < 2 && nq > 5) {
                 float hq = 0.0f;
 #pragma unroll
                 for (int w = 0; w < TB_NW; ++w) hq += sh.wp[w][lane][4 + wave];
-                __hip_atomic_store(rec + 5 + wave, ((unsigned long long)tag << 32) | __float_as_uint(hq),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                publish(rec + 5 + wave, tag, __float_as_uint(hq));
             }
         }
         }
@@ -583,9 +541,11 @@ __device__ __forceinline__ TbSolved trajb_solve(
                 const int w = wave * WAVE + lane;
                 const bool mine = w < G;
                 gu64 *p = A + ((size_t)b * MAX_COOP_WG + (mine ? w : 0)) * XCHG3_GRANULES;
+                float val[TB_NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                // (bounded_wait written out: through the helper the loop's exit takes three more taken branches,
+                //  0.07 us per solve at N = 4096, where a lone wave's instruction stream is the whole cost)
                 const unsigned long long t0 = wall_clock64();
                 bool timeout = false;
-                float val[TB_NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
                 for (unsigned spin = 0;; ++spin) {
                     const bool ok = load_rec(p, tag, nq, val) || !mine;
                     if (__all(ok)) break;
@@ -652,24 +612,20 @@ __device__ __forceinline__ TbSolved trajb_solve(
                     const size_t slot = ((size_t)(ptag & 1u) * TJ_MAXK + b) * MAX_PEERS;
                     if (mine) {
                         gu64 *dst = (gu64 *)(uintptr_t)pt->inbox[r] + (slot + prank) * 8 + gq;
-                        __hip_atomic_store(dst, ((unsigned long long)ptag << 32) | __float_as_uint(val),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        publish<__HIP_MEMORY_SCOPE_SYSTEM>(dst, ptag, __float_as_uint(val));
                     }
                     gu64 *src = (gu64 *)(uintptr_t)pt->inbox[prank] + (slot + (mine ? r : prank)) * 8 + (mine ? gq : 0);
-                    const unsigned long long t0 = wall_clock64();
                     unsigned long long got = 0ull;
-                    bool timeout = false;
-                    for (unsigned spin = 0;; ++spin) {
+                    const bool timeout = !bounded_wait(wall_clock64(), spin_ticks, [&] {
                         got = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        const bool ok = !mine || (uint32_t)(got >> 32) == ptag;
-                        if (__all(ok)) break;
-                        if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-                    }
+                        const bool ok = !mine || granule_has(got, ptag);
+                        return __all(ok) != 0;
+                    });
                     if (timeout) {
                         if (lane == 0) { atomicOr(&hdr->status, RLVI_ST_TIMEOUT); sh.out.dead = 1; }
                         xdead = true;
                     }
-                    const float pv = __uint_as_float((uint32_t)got);
+                    const float pv = __uint_as_float(granule_payload(got));
                     double acc = mine ? (double)pv : (gq == 4 ? (double)__builtin_inff() : 0.0);
 #pragma unroll
                     for (int m = 8; m < WAVE; m <<= 1) {
@@ -683,9 +639,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
                     dbg[989] = wall_clock64();
                 }
                 if (gq < nq && !xdead)
-                    __hip_atomic_store(B + ((size_t)(cl >> 3) * TJ_MAXK + b) * XCHG3_GRANULES + gq,
-                                       ((unsigned long long)tag << 32) | __float_as_uint(val),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    publish(B + ((size_t)(cl >> 3) * TJ_MAXK + b) * XCHG3_GRANULES + gq, tag, __float_as_uint(val));
             }
         }
         TB_STAMP();   // published
@@ -696,6 +650,8 @@ __device__ __forceinline__ TbSolved trajb_solve(
             if (!dead) {
                 const bool mine = lane < Ke;
                 gu64 *p = B + ((size_t)(b & (XCHG3B_REPLICAS - 1)) * TJ_MAXK + (mine ? lane : 0)) * XCHG3_GRANULES;
+                // (bounded_wait written out: through the helper the loop's exit takes three more taken branches,
+                //  0.07 us per solve at N = 4096, where a lone wave's instruction stream is the whole cost)
                 const unsigned long long t0 = wall_clock64();
                 bool timeout = false;
                 for (unsigned spin = 0;; ++spin) {
@@ -775,8 +731,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
             state->shift = gmin;
             state->it = it;
             if (pt != nullptr) pt->dtag = ptag - 1u;
-            __hip_atomic_store((gu32 *)&hdr->epoch_base, tag + 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            close_tags(hdr, tag);
         }
         if (tid < K) state->nodes[tid] = rn_l;
     }

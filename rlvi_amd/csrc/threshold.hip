@@ -206,7 +206,7 @@ __global__ __launch_bounds__(THR_BLOCK) void threshold_kernel(float *__restrict_
 // fp32 bit pattern is an order-preserving key.  c* -- the smallest key c such that the keys >= c
 // fit together -- is found 8 bits per pass, most significant first: every workgroup builds a
 // 256-bin histogram {count, sum of (1-pi) units, smallest key} of its keys inside the current
-// prefix, ONE two-stage record exchange (the protocol of estep_trajb.hip: workgroup w publishes a
+// prefix, ONE two-stage record exchange (on the exchange layer of rlvi_coop.h: workgroup w publishes a
 // record per bin, workgroup b adds bin b's records in a fixed order and publishes the total in 8
 // replicas, everybody reads the 256 totals) gives every workgroup identical totals, a suffix scan
 // finds the first bin whose suffix fits, and the descent continues in the bin below it.  Four
@@ -222,7 +222,6 @@ __global__ __launch_bounds__(THR_BLOCK) void threshold_kernel(float *__restrict_
 constexpr int THQ_BLOCK = 256;
 constexpr unsigned long long THQ_ONE = 1ull << 40;      // one key in the packed {count, sum} LDS word
 constexpr int THQ_NW = THQ_BLOCK / WAVE;
-typedef unsigned int thq_vu4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t one_minus_u(float p) {
     return (uint32_t)__float2uint_rn((1.0f - p) * 16777216.0f);
@@ -280,32 +279,14 @@ struct ThqShared {
     unsigned long long stamps[60];     // RLVI_THR_DEBUG only
 };
 
-// 32-byte record = four granules {tag32 | payload32}: {count, min key, sum lo, sum hi}
-__device__ __forceinline__ void thq_store(gu64 *p, uint32_t tag, uint32_t cnt, uint32_t mn,
-                                          unsigned long long sum) {
-    // two 16-byte write-through stores; every 8-byte granule carries its own tag, so tearing
-    // between granules is harmless
-    const thq_vu4 q0 = {cnt, tag, mn, tag};
-    const thq_vu4 q1 = {(uint32_t)sum, tag, (uint32_t)(sum >> 32), tag};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\t"
-                 "global_store_dwordx4 %0, %2, off offset:16 sc1\n\t"
-                 "s_nop 1"
-                 :
-                 : "v"((unsigned long long)(uintptr_t)p), "v"(q0), "v"(q1)
-                 : "memory");
-}
+// 32-byte record = four granules (rlvi_coop.h): {count, min key, sum lo, sum hi}
 __device__ __forceinline__ bool thq_load(gu64 *p, uint32_t tag, uint32_t &cnt, uint32_t &mn,
                                          unsigned long long &sum) {
-    thq_vu4 q0, q1;
-    asm volatile("global_load_dwordx4 %0, %2, off sc1\n\t"
-                 "global_load_dwordx4 %1, %2, off offset:16 sc1\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(q0), "=&v"(q1)
-                 : "v"((unsigned long long)(uintptr_t)p)
-                 : "memory");
-    cnt = q0.x; mn = q0.z;
-    sum = ((unsigned long long)q1.z << 32) | q1.x;
-    return q0.y == tag && q0.w == tag && q1.y == tag && q1.w == tag;
+    vu4 q[2];
+    rec_load<2>(p, q);
+    cnt = q[0].x; mn = q[0].z;
+    sum = ((unsigned long long)q[1].z << 32) | q[1].x;
+    return rec_tagged<4>(q, tag);
 }
 
 // Totals of the per-workgroup histograms sh.h[0 .. NH-1] over the G workgroups, back into sh.h
@@ -340,19 +321,15 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
     for (int j = 0; j < 2 * NH; ++j) {
         const int c = j * THQ_BLOCK + tid;
         const int rec = c >> 1, hf = rec >> 8, bin = rec & (THR_BINS - 1);
-        thq_vu4 q;
+        vu4 q;
         if (c & 1) {
             const unsigned long long sm = sh.h[hf].sum[bin];
-            q = (thq_vu4){(uint32_t)sm, tag, (uint32_t)(sm >> 32), tag};
+            q = granule_pair(tag, (uint32_t)sm, (uint32_t)(sm >> 32));
         } else {
-            q = (thq_vu4){sh.h[hf].cnt[bin], tag, sh.h[hf].mn[bin], tag};
+            q = granule_pair(tag, sh.h[hf].cnt[bin], sh.h[hf].mn[bin]);
         }
         if (!(COARSE0 && hf == 0) || thq_coarse_bin(bin))
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
-                     :
-                     : "v"((unsigned long long)(uintptr_t)(A + (size_t)b * NREC * XCHG4_GRANULES) + (unsigned long long)c * 16ull),
-                       "v"(q)
-                     : "memory");
+            rec_store16(A + (size_t)b * NREC * XCHG4_GRANULES + (size_t)c * 2, q);
     }
     THQ_STAMP();   // stage A stored
     // ---- stage B: workgroup b adds the records of its 256 / G bins (G is 64, 128 or 256): G / 64
@@ -363,28 +340,23 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
         const int wg = (wave % wpb) * WAVE + lane;           // the workgroup whose records this lane reads
         uint32_t c[NH], mn[NH];
         unsigned long long sm[NH];
-        bool timeout = false;
-        {
-            const unsigned long long t0 = wall_clock64();
-            bool got[NH];
+        bool got[NH];
+#pragma unroll
+        for (int hf = 0; hf < NH; ++hf) {
+            got[hf] = COARSE0 && hf == 0 && !thq_coarse_bin(bin);
+            c[hf] = 0u; mn[hf] = 0xFFFFFFFFu; sm[hf] = 0ull;
+        }
+        const bool timeout = !bounded_wait(wall_clock64(), spin_ticks, [&] {
+            bool all = true;
 #pragma unroll
             for (int hf = 0; hf < NH; ++hf) {
-                got[hf] = COARSE0 && hf == 0 && !thq_coarse_bin(bin);
-                c[hf] = 0u; mn[hf] = 0xFFFFFFFFu; sm[hf] = 0ull;
+                if (!got[hf])
+                    got[hf] = thq_load(A + ((size_t)wg * NREC + hf * THR_BINS + bin) * XCHG4_GRANULES, tag,
+                                       c[hf], mn[hf], sm[hf]);
+                all = all && got[hf];
             }
-            for (unsigned spin = 0;; ++spin) {
-                bool all = true;
-#pragma unroll
-                for (int hf = 0; hf < NH; ++hf) {
-                    if (!got[hf])
-                        got[hf] = thq_load(A + ((size_t)wg * NREC + hf * THR_BINS + bin) * XCHG4_GRANULES, tag,
-                                           c[hf], mn[hf], sm[hf]);
-                    all = all && got[hf];
-                }
-                if (all) break;
-                if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-            }
-        }
+            return all;
+        });
         if (timeout) sh.dead = 1;
         THQ_STAMP();   // gathered
 #pragma unroll
@@ -418,22 +390,18 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
                     const size_t slot = ((size_t)(ptag & 1u) * NREC + hf * THR_BINS + bin) * MAX_PEERS;
                     if (mine) {
                         gu64 *dst = (gu64 *)(uintptr_t)(pt->inbox[r] + PEER_ESTEP_BYTES) + (slot + prank) * 4 + gq;
-                        __hip_atomic_store(dst, ((unsigned long long)ptag << 32) | mv, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_SYSTEM);
+                        publish<__HIP_MEMORY_SCOPE_SYSTEM>(dst, ptag, mv);
                     }
                     gu64 *src = (gu64 *)(uintptr_t)(pt->inbox[prank] + PEER_ESTEP_BYTES) + (slot + (mine ? r : prank)) * 4 + gq;
-                    const unsigned long long t0 = wall_clock64();
                     unsigned long long got = 0ull;
-                    bool timeout = false;
-                    for (unsigned spin = 0;; ++spin) {
+                    const bool timeout = !bounded_wait(wall_clock64(), spin_ticks, [&] {
                         got = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        const bool ok = !mine || (uint32_t)(got >> 32) == ptag;
+                        const bool ok = !mine || granule_has(got, ptag);
                         // (lanes 0..31 of this wave: the others have left the branch)
-                        if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
-                        if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-                    }
+                        return __builtin_amdgcn_ballot_w64(!ok) == 0ull;
+                    });
                     if (timeout) sh.dead = 1;
-                    const uint32_t pv = (uint32_t)got;
+                    const uint32_t pv = granule_payload(got);
                     const uint32_t hi = (uint32_t)__shfl_down((int)pv, 1, WAVE);          // gq == 2: the hi half sits one lane up
                     unsigned long long acc = !mine ? (gq == 1 ? 0xFFFFFFFFull : 0ull)
                                              : gq == 2 ? (((unsigned long long)hi << 32) | pv) : (unsigned long long)pv;
@@ -449,10 +417,7 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
                 }
                 const uint32_t v = gq == 0 ? (uint32_t)tc : gq == 1 ? tm : gq == 2 ? (uint32_t)ts
                                                                            : (uint32_t)(ts >> 32);
-                if (sh.dead == 0)
-                __hip_atomic_store(B + ((size_t)rep * NREC + hf * THR_BINS + bin) * XCHG4_GRANULES + gq,
-                                   ((unsigned long long)tag << 32) | v, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                if (sh.dead == 0) publish(B + ((size_t)rep * NREC + hf * THR_BINS + bin) * XCHG4_GRANULES + gq, tag, v);
             }
         }
         THQ_STAMP();   // published
@@ -466,11 +431,10 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
 #pragma unroll
         for (int hf = 0; hf < NH; ++hf) { c[hf] = 0; mn[hf] = 0xFFFFFFFFu; sm[hf] = 0ull; }
         if (sh.dead == 0) {
-            const unsigned long long t0 = wall_clock64();
             bool got[NH];
 #pragma unroll
             for (int hf = 0; hf < NH; ++hf) got[hf] = COARSE0 && hf == 0 && !thq_coarse_bin(tid);
-            for (unsigned spin = 0;; ++spin) {
+            timeout = !bounded_wait(wall_clock64(), spin_ticks, [&] {
                 bool all = true;
 #pragma unroll
                 for (int hf = 0; hf < NH; ++hf) {
@@ -479,9 +443,8 @@ __device__ __forceinline__ bool thq_exchange(ThqShared &sh, gu64 *bufA, gu64 *bu
                                                    XCHG4_GRANULES, tag, c[hf], mn[hf], sm[hf]);
                     all = all && got[hf];
                 }
-                if (all) break;
-                if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-            }
+                return all;
+            });
         }
         if (timeout) sh.dead = 1;
 #pragma unroll
@@ -511,11 +474,7 @@ __device__ __forceinline__ int thq_list_hop(ThqShared &sh, gu64 *bufA, uint32_t 
         uint32_t k0 = 2 * tid < (int)n ? sh.lkeys[2 * tid] : THQ_LIST_NONE;
         const uint32_t k1 = 2 * tid + 1 < (int)n ? sh.lkeys[2 * tid + 1] : THQ_LIST_NONE;
         if (tid == 0 && n > (uint32_t)THQ_LIST_CAP) k0 = THQ_LIST_OVER;
-        const thq_vu4 q = {k0, tag, k1, tag};
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
-                     :
-                     : "v"((unsigned long long)(uintptr_t)(Lst + (size_t)b * THQ_LIST_CAP) + (unsigned long long)tid * 16ull), "v"(q)
-                     : "memory");
+        rec_store16(Lst + (size_t)b * THQ_LIST_CAP + (size_t)tid * 2, granule_pair(tag, k0, k1));
     }
     // 512 / 1024 / 2048 pairs: 2 / 4 / 8 per thread, four loads in flight at a time (a pair past the end re-reads
     // this thread's first one: always valid)
@@ -533,22 +492,14 @@ __device__ __forceinline__ int thq_list_hop(ThqShared &sh, gu64 *bufA, uint32_t 
             want[q] = pr < npairs;
             addr[q] = (unsigned long long)(uintptr_t)Lst + (unsigned long long)(want[q] ? pr : tid) * 16ull;
         }
-        thq_vu4 v[4];
-        for (unsigned spin = 0;; ++spin) {
-            asm volatile("global_load_dwordx4 %0, %4, off sc1\n\t"
-                         "global_load_dwordx4 %1, %5, off sc1\n\t"
-                         "global_load_dwordx4 %2, %6, off sc1\n\t"
-                         "global_load_dwordx4 %3, %7, off sc1\n\t"
-                         "s_waitcnt vmcnt(0)"
-                         : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-                         : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3])
-                         : "memory");
+        vu4 v[4];
+        timeout = !bounded_wait(t0, spin_ticks, [&] {        // (one t0 for all groups)
+            rec_load_scattered(addr, v);
             bool all = true;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) all = all && v[q].y == tag && v[q].w == tag;
-            if (all) break;
-            if ((spin & 63u) == 63u && wall_clock64() - t0 > spin_ticks) { timeout = true; break; }
-        }
+            for (int q = 0; q < 4; ++q) all = all && rec_tagged<2>(&v[q], tag);
+            return all;
+        });
         if (timeout) break;
         // this thread's keys into the dense list (any order: the histograms add integers)
 #pragma unroll
@@ -595,9 +546,8 @@ __global__ __launch_bounds__(THQ_BLOCK) void threshold_radix_kernel(
     gu64 *bufA = (gu64 *)(reinterpret_cast<unsigned long long *>(wsb + WS_XCHG4A_OFF));
     gu64 *bufB = (gu64 *)(reinterpret_cast<unsigned long long *>(wsb + WS_XCHG4B_OFF));
     ThrState *state = reinterpret_cast<ThrState *>(wsb + (pt != nullptr ? WS_PEER_STATE_OFF + 384 : WS_THRSTATE_OFF));
-    uint32_t tag = __hip_atomic_load((gu32 *)&hdr->epoch_base, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT) + 1u;
-    const unsigned long long spin_ticks = spin_bound(hdr) * (pt != nullptr ? 100ull : 1ull);
+    uint32_t tag = first_tag(hdr);
+    const unsigned long long spin_ticks = spin_bound(hdr, pt != nullptr);
     uint32_t ptag = pt != nullptr ? pt->dtag + 1u : 0u;
     int xstep = 0;
     if (tid == 0) sh.dead = 0;
@@ -914,7 +864,7 @@ __global__ __launch_bounds__(THQ_BLOCK) void threshold_radix_kernel(
             for (int q = 0; q < dbgi; ++q) dbg[q] = sh.stamps[q];
             dbg[63] = (unsigned long long)dbgi;
         }
-        __hip_atomic_store((gu32 *)&hdr->epoch_base, tag + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        close_tags(hdr, tag);
     }
     if (hand_over && b == 0) {       // (nobody has written anything: every workgroup left at the first exchange)
         __syncthreads();
