@@ -40,6 +40,22 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     int flags, float tol, int32_t *__restrict__ out_iters, float *__restrict__ trace,
     float *__restrict__ mstep_out, double mstep_scale, unsigned long long *__restrict__ dbg,
     PeerTable *__restrict__ pt) {
+    // The parameter list as the argument block lays it out (the lab build reads the late arguments from it by hand,
+    // below).  The first late member sits at the preload boundary that rlvi_amd/_build.py documents.
+    struct TbKernArgs {
+        float *res, *wts;
+        void *ws;
+        int64_t N, Nall;
+        int Ls, G, K, flags;
+        float tol;
+        int32_t *out_iters;
+        float *trace, *mstep_out;
+        double mstep_scale;
+        unsigned long long *dbg;
+        PeerTable *pt;
+    };
+    static_assert(offsetof(TbKernArgs, tol) == 56, "the late arguments begin where the preloaded ones end");
+    static_assert(sizeof(TbKernArgs) == 112, "one member per kernel parameter, in order");
     // Argument order = order of first use: the first 56 bytes (res ... flags) are preloaded into SGPRs at wave
     // start (rlvi_amd/_build.py: kernarg preload) and are all that the slice loads and the warm-start state's
     // loads need; the rest is asked for in one burst and waited for once, behind those loads (the pin below).
@@ -53,11 +69,11 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     const int tid = threadIdx.x;
 #if RLVI_STAMPS
     // (lab build: the wall clock as the kernel's very first instruction -- it needs no argument --, stored with the
-    //  other stamps once dbg is known: dbg[986] entry, [987] first data loads issued, [988] slice landed;
+    //  other stamps once dbg is known: ENTRY = {entry, first data loads issued, slice landed} (rlvi_stamps.h);
     //  shader clock of this launch = delta s_memtime / delta s_memrealtime x 100 MHz)
     // The compiler puts its own fetch of the arguments past the preloaded ones at the top of the kernel, in front
     // of anything written here.  So this build does not touch those parameters: it reads them from the argument
-    // block itself, through a pointer that exists only behind the stamp (offsets = the signature's layout).
+    // block itself, through a pointer that exists only behind the stamp (offsets: TbKernArgs below).
     unsigned long long rt0;
     typedef const __attribute__((address_space(4))) char *tb_ka_t;
     tb_ka_t ka = (tb_ka_t)__builtin_amdgcn_kernarg_segment_ptr();
@@ -91,14 +107,14 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     // The warm-start state's loads go out beside the slice loads (one round trip for both), and so does the
     // request for the arguments past the preloaded ones: one wait for all of it.
 #if RLVI_STAMPS
-#define TB_LATE(T, off) (*(T const __attribute__((address_space(4))) *)(ka + (off)))
-    tol = TB_LATE(float, 56);
-    out_iters = TB_LATE(int32_t *, 64);
-    trace = TB_LATE(float *, 72);
-    mstep_out = TB_LATE(float *, 80);
-    mstep_scale = TB_LATE(double, 88);
-    dbg = TB_LATE(unsigned long long *, 96);
-    pt = TB_LATE(PeerTable *, 104);
+#define TB_LATE(member) (*(decltype(TbKernArgs::member) const __attribute__((address_space(4))) *)(ka + offsetof(TbKernArgs, member)))
+    tol = TB_LATE(tol);
+    out_iters = TB_LATE(out_iters);
+    trace = TB_LATE(trace);
+    mstep_out = TB_LATE(mstep_out);
+    mstep_scale = TB_LATE(mstep_scale);
+    dbg = TB_LATE(dbg);
+    pt = TB_LATE(pt);
 #undef TB_LATE
 #endif
     TbWarmRaw raw = tb_warm_issue(ws, (flags & TBF_SHARDED) != 0);
@@ -107,11 +123,11 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     const TbWarm wm = tb_warm_select<tb_early_nodes(E, TB_BLOCK)>(raw, Nall, K, (flags & TBF_COLD) != 0);
 #if RLVI_STAMPS
     if (dbg != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        dbg[986] = rt0;                                   // entry: the kernel's very first instruction
-        dbg[987] = rt1;                                   // first data loads issued
+        stamp_put<ST_ENTRY>(dbg, true, 0, rt0);           // entry: the kernel's very first instruction
+        stamp_put<ST_ENTRY>(dbg, true, 1, rt1);           // first data loads issued
         float keep = l[0] + q0[0];
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(keep) : : "memory");
-        dbg[988] = __builtin_amdgcn_s_memrealtime();      // slice landed
+        stamp_clock<ST_ENTRY>(dbg, true, 2);              // slice landed
     }
 #endif
     const TbSolved s = trajb_solve<E, TB_BLOCK>(sh, wm, l, q0, ev, true, b, G, Nall, tol, K, out_iters, trace,
@@ -119,10 +135,8 @@ __global__ __launch_bounds__(TB_BLOCK, (TB_BLOCK == 256 && E == 1 && !RLVI_STAMP
     // a wait that timed out (RLVI_ST_TIMEOUT: the workgroups were not all resident) leaves the
     // caller's residuals and pi as they were -- the host raises on the status; it never hands out garbage
 #if RLVI_STAMPS
-    if (dbg != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        dbg[960] = __builtin_amdgcn_s_memtime() - clk0;
-        dbg[961] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
+    stamp_put<ST_KERNEL_CYCLES>(dbg, blockIdx.x == 0 && threadIdx.x == 0, 0, __builtin_amdgcn_s_memtime() - clk0);
+    stamp_put<ST_KERNEL_TICKS>(dbg, blockIdx.x == 0 && threadIdx.x == 0, 0, __builtin_amdgcn_s_memrealtime() - rt0);
 #endif
     if (s.dead) return;
     const float pmax = tb_pmax(s);

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(FE_THREADS) void fused_em_kernel(
     WsHeader *hdr = reinterpret_cast<WsHeader *>(ws);
 
     // RLVI_TJ_DEBUG: wall-clock stamps (100 MHz) of workgroup 0's phases, behind the solve's own
-#define FE_STAMP(k) do { if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && tid == 0) dbg[970 + (k)] = wall_clock64(); } while (0)
+#define FE_STAMP(k) stamp_clock<ST_FUSED_SEQ>(dbg, RLVI_STAMPS && b == 0 && tid == 0, k)
     FE_STAMP(0);
     const int64_t wg_row0 = (int64_t)b * FE_ROWS;
     const int64_t wrow0 = wg_row0 + (int64_t)wave * FE_TPW * FE_R;

@@ -8,14 +8,7 @@
 #include <utility>
 
 #include "rlvi_hip.h"
-
-// In-kernel wall-clock stamps and value dumps of the cooperating kernels (RLVI_TJ_DEBUG / RLVI_THR_DEBUG
-// at run time) exist only in a -DRLVI_STAMPS=1 build (tools/build_variants.py stamps; load it with
-// RLVI_LIB_PATH): in the product build they are compiled out -- the stamp pointer, its counter and the
-// guards around every dump cost the trajectory kernels some twenty registers, i.e. a wave per SIMD.
-#ifndef RLVI_STAMPS
-#define RLVI_STAMPS 0
-#endif
+#include "rlvi_stamps.h"     // RLVI_STAMPS (0: the product build) and the lab builds' slot table
 
 namespace rlvi {
 
@@ -155,11 +148,19 @@ constexpr size_t PEER_THR_BYTES = 2ull * 512 * MAX_PEERS * 4 * 8;
 constexpr size_t PEER_INBOX_BYTES = PEER_ESTEP_BYTES + PEER_THR_BYTES;
 constexpr size_t WS_SCRATCH_OFF = WS_PEER_OFF + WS_PEER_BYTES;
 
+// the lab stamps' slot table (rlvi_stamps.h) starts at the scratch region's first byte
+inline unsigned long long *stamp_base(void *ws) {
+    return reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF);
+}
+
 __host__ __device__ inline size_t ws_bytes_for(int64_t max_n, int64_t max_b) {
-    // scratch: two fp32 vectors of max(max_n, max_b) (fused E+M keeps l and e there)
+    // scratch: two fp32 vectors of max(max_n, max_b) (fused E+M keeps l and e there); a stamps build: the whole slot
+    // table at least
     int64_t m = max_n > max_b ? max_n : max_b;
     if (m < 0) m = 0;
-    size_t s = WS_SCRATCH_OFF + (size_t)m * 8 + 256;
+    size_t scratch = (size_t)m * 8;
+    if (RLVI_STAMPS && scratch < STAMP_BYTES) scratch = STAMP_BYTES;
+    size_t s = WS_SCRATCH_OFF + scratch + 256;
     return (s + 255) & ~(size_t)255;
 }
 

@@ -102,11 +102,11 @@ __device__ __forceinline__ void wave_sort_keys(float &key, int &src) {
 // while the recurrence wave is in its serial chain (a lone wave issues one vector instruction per ~6 clocks
 // whatever it depends on: nothing can be tucked into the chain's stalls on the SAME wave).  The expressions
 // are the ones tj_chain had, operand for operand; every lane of the helper wave calls, between the two
-// workgroup barriers of tj_chain<true, true, true>.
+// workgroup barriers of tj_chain<true, true>.
 __device__ __forceinline__ void tj_accept_guess(TjSplit &sp, int xstep, unsigned long long *dbg) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & (WAVE - 1);
-    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[996] = wall_clock64();
+    stamp_clock<ST_HELPER>(dbg, RLVI_STAMPS && blockIdx.x == 0 && xstep == 0 && lane == 0, 0);
     const float rn = sp.rn_ihq[lane];
     const float err_l = sp.err_lrq[lane];
     const int steps = __builtin_amdgcn_readfirstlane(sp.steps);
@@ -134,7 +134,7 @@ __device__ __forceinline__ void tj_accept_guess(TjSplit &sp, int xstep, unsigned
     sp.rn_ihq[lane] = ihq;
     sp.err_lrq[lane] = lrq;
     sp.slope[lane] = slope;
-    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[997] = wall_clock64();
+    stamp_clock<ST_HELPER>(dbg, RLVI_STAMPS && blockIdx.x == 0 && xstep == 0 && lane == 0, 1);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -144,8 +144,6 @@ __device__ __forceinline__ void tj_accept_guess(TjSplit &sp, int xstep, unsigned
 // samples, for j < Ke (the evaluated nodes); Ka >= Ke nodes are kept in the state.  FIRST: the
 // sums were taken with e' = exp(-(l - shift)) and gmin (any lane's value is min-reduced here) is
 // the true minimum.  Results go to `out` (lane 0 / lanes < Ka); every lane must call.
-// HASQ: tQ is meaningful (second-order local model, quintic global model); otherwise first-order /
-// cubic.
 // ---------------------------------------------------------------------------------------
 // HI (first round of estep_trajb.hip): tR3 = sum e^3/(1+re)^4 and tR4 = sum e^4/(1+re)^5 (the third- and
 // fourth-order terms of S around the node) are given too; the chain then runs on the fourth-order
@@ -153,7 +151,7 @@ __device__ __forceinline__ void tj_accept_guess(TjSplit &sp, int xstep, unsigned
 // whatever the data: one behind the operand table, one in front of the acceptance test; between them another wave
 // of the workgroup runs tj_accept_guess on `sp` and every remaining wave just passes the two barriers
 // (trajb_solve).
-template <bool FIRST, bool HASQ = true, bool HI = false>
+template <bool FIRST, bool HI = false>
 __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, float tP, float tQ,
                                          float tD,
                                          float gmin, bool dead, float rn_l, float shift, float invN,
@@ -163,8 +161,9 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
     static_assert(!HI || FIRST, "the fourth-order sums are taken in the first round only");
     const int lane = threadIdx.x & (WAVE - 1);
     const bool has = lane < Ke;
-    // RLVI_TJ_DEBUG: where the recurrence wave's time goes (first round of workgroup 0)
-#define TJ_STAMP(k) do { if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[990 + (k)] = wall_clock64(); } while (0)
+    // RLVI_TJ_DEBUG (rlvi_stamps.h): where the recurrence wave's time goes and what it saw, first round of workgroup 0
+    const bool lab0 = RLVI_STAMPS && blockIdx.x == 0 && xstep == 0;
+#define TJ_STAMP(k) stamp_clock<ST_CHAIN_SEQ>(dbg, lab0 && lane == 0, k)
     TJ_STAMP(0);
     float scale = 1.0f;
     if (FIRST) {
@@ -180,9 +179,13 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
     bool finite = has ? (tS < finf && tP < finf && tD < finf && tQ < finf) : true;
     if (HI && has) finite = finite && tR3 < finf && tR4 < finf;
     const bool round_ok = __all(finite) && scale > 1e-6f && scale < 1e6f && !dead;
-    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0) {
-        if (lane < 8) { dbg[104 + 3 * lane] = (unsigned long long)__double_as_longlong((double)tS); dbg[105 + 3 * lane] = (unsigned long long)__double_as_longlong((double)tP); dbg[106 + 3 * lane] = (unsigned long long)__double_as_longlong((double)tQ); }
-        if (lane == 0) { dbg[102] = __ballot(finite); dbg[103] = __float_as_uint(scale); }
+    {
+        auto f64_bits = [](float v) { return (unsigned long long)__double_as_longlong((double)v); };
+        stamp_put<ST_TJ_TOTALS>(dbg, lab0 && lane < 8, 3 * lane, f64_bits(tS));
+        stamp_put<ST_TJ_TOTALS>(dbg, lab0 && lane < 8, 3 * lane + 1, f64_bits(tP));
+        stamp_put<ST_TJ_TOTALS>(dbg, lab0 && lane < 8, 3 * lane + 2, f64_bits(tQ));
+        stamp_put<ST_TJ_FINITE>(dbg, lab0 && lane == 0, 0, __ballot(finite));
+        stamp_put<ST_TJ_SCALE>(dbg, lab0 && lane == 0, 0, (unsigned long long)__float_as_uint(scale));
     }
 
     // lane-parallel: a0 = mean(pi) at the node, b = d mean / dr, err = ||new - old||_2
@@ -332,7 +335,7 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
         // Cold or poor guesses: the nodes are far from the trajectory, but together they sample
         // S(r) over its whole range.  s(u) = mean(pi) as a function of u = log r is a sum of
         // logistic sigmoids -- smooth and monotone -- so a two-point Hermite interpolant between
-        // the evaluated nodes that bracket the current r (values, slopes and, with HASQ, second
+        // the evaluated nodes that bracket the current r (values, slopes and second
         // derivatives: quintic, error ~h^6/46080 |s^(6)| at spacing h = ln 2) gives every step of
         // the recurrence to ~1e-5 whatever the guess was; the next round's local model finishes.
         // Outside the sampled range: the damped local model of the nearest node (+-50 %).
@@ -370,17 +373,11 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
             const float h = key - ua;
             const bool okiv = lane >= 1 && lane < nv && h > 1e-5f;
             const float df = s0_s - fa, g0 = h * da, g1 = h * s1_s;
-            float c2, c3, c4 = 0.0f, c5 = 0.0f;
-            if (HASQ) {
-                const float q0 = h * h * ea, q1 = h * h * s2_s;
-                c2 = 0.5f * q0;
-                c3 = fmaf(10.0f, df, fmaf(-6.0f, g0, fmaf(-4.0f, g1, fmaf(-1.5f, q0, 0.5f * q1))));
-                c4 = fmaf(-15.0f, df, fmaf(8.0f, g0, fmaf(7.0f, g1, fmaf(1.5f, q0, -q1))));
-                c5 = fmaf(6.0f, df, fmaf(-3.0f, g0, fmaf(-3.0f, g1, fmaf(-0.5f, q0, 0.5f * q1))));
-            } else {
-                c2 = fmaf(3.0f, df, fmaf(-2.0f, g0, -g1));
-                c3 = fmaf(-2.0f, df, g0 + g1);
-            }
+            const float q0 = h * h * ea, q1 = h * h * s2_s;
+            const float c2 = 0.5f * q0;
+            const float c3 = fmaf(10.0f, df, fmaf(-6.0f, g0, fmaf(-4.0f, g1, fmaf(-1.5f, q0, 0.5f * q1))));
+            const float c4 = fmaf(-15.0f, df, fmaf(8.0f, g0, fmaf(7.0f, g1, fmaf(1.5f, q0, -q1))));
+            const float c5 = fmaf(6.0f, df, fmaf(-3.0f, g0, fmaf(-3.0f, g1, fmaf(-0.5f, q0, 0.5f * q1))));
             float *cf = out.coef[lane];
             *reinterpret_cast<float4 *>(cf) = make_float4(fa, g0, c2, c3);
             *reinterpret_cast<float4 *>(cf + 4) = make_float4(c4, c5, ua, okiv ? __builtin_amdgcn_rcpf(h) : -1.0f);
@@ -443,7 +440,7 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
     // (the second barrier: the helper wave's half of the test is in `sp` behind it -- long since, it is a tenth
     //  of the chain)
     if (HI) __syncthreads();
-    if ((RLVI_STAMPS && dbg != nullptr) && HI && blockIdx.x == 0 && xstep == 0 && lane == 0) dbg[998] = wall_clock64();
+    stamp_clock<ST_CHAIN_BARRIER2>(dbg, HI && lab0 && lane == 0);
     int it_acc = 0;
     bool accept_now = false;
     if (HI && FIRST && __all(inside) && !scanned && round_ok && trace == nullptr && steps >= 2) {
@@ -463,8 +460,7 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
         const bool act = live && lane + 1 < steps;
         float of = act ? rem * iom2 * irn : 0.0f;                            // rho_k
         float sc = act ? fminf(fabsf(b_l) * rnew_l * iom2 * irn, 1.0f) : 0.0f;   // s_k
-        if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0)
-            dbg[828 + lane] = ((unsigned long long)__float_as_uint(sc) << 32) | __float_as_uint(of);
+        stamp_put<ST_TJ_SK_RHO>(dbg, lab0, lane, sc, of);
         affine_scan(sc, of);                                                 // x -> sc x + of, inclusive
         float Ek = lane_up1(of);                                             // bound on |r_k - true| / r_k
         if (lane == 0) Ek = 0.0f;                                            // r_0 is exact
@@ -495,11 +491,9 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
             const unsigned long long upto = ks >= 63 ? ~0ull : ((2ull << ks) - 1ull);
             if ((unclear & upto) == 0ull && ks + 1 <= steps) { accept_now = true; it_acc = ks + 1; }
         }
-        if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0) {
-            dbg[700 + lane] = ((unsigned long long)__float_as_uint(err_e) << 32) | __float_as_uint(band);
-            dbg[764 + lane] = ((unsigned long long)__float_as_uint(Ek) << 32) | __float_as_uint(slope);
-            if (lane == 0) dbg[699] = ((unsigned long long)(accept_now ? 1 : 0) << 32) | (unsigned)it_acc;
-        }
+        stamp_put<ST_TJ_ERR_BAND>(dbg, lab0, lane, err_e, band);
+        stamp_put<ST_TJ_EK_SLOPE>(dbg, lab0, lane, Ek, slope);
+        stamp_put<ST_TJ_ACCEPT>(dbg, lab0 && lane == 0, 0, accept_now ? 1u : 0u, (unsigned)it_acc);
     }
     TJ_STAMP(4);   // acceptance test done
     // Early accept: with nodes off by delta the corrected r are good to 0.25 delta^2, and the
@@ -518,12 +512,10 @@ __device__ __forceinline__ void tj_chain(TjOut &out, int Ke, int Ka, float tS, f
         const bool unsafe = has && lane < it_now && fabsf(err_l - tol) <= u * err_l;
         if (__ballot(unsafe) == 0ull) delta_w = 0.0f;
     }
-    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep < 4)
-        dbg[400 + xstep * 64 + lane] = ((unsigned long long)__float_as_uint(rn) << 32) | __float_as_uint(rnew_l);
-    if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && xstep == 0) {
-        dbg[130 + lane] = ((unsigned long long)__float_as_uint(rn) << 32) | __float_as_uint(rnew_l);
-        if (lane == 0) { dbg[128] = round_ok; dbg[129] = ((unsigned long long)it_now << 32) | __float_as_uint(delta_w); }
-    }
+    stamp_put<ST_TJ_ROUND_NODES>(dbg, RLVI_STAMPS && blockIdx.x == 0 && xstep < 4, xstep * WAVE + lane, rn, rnew_l);
+    stamp_put<ST_TJ_NODES>(dbg, lab0, lane, rn, rnew_l);
+    stamp_put<ST_TJ_ROUND_OK>(dbg, lab0 && lane == 0, 0, (unsigned long long)round_ok);
+    stamp_put<ST_TJ_IT_DELTA>(dbg, lab0 && lane == 0, 0, (unsigned)it_now, __float_as_uint(delta_w));
     // guesses stay where sums in fp32 cannot underflow; an invalid round restarts from the
     // geometric cold guess instead of re-evaluating the nodes that broke it; a round that did not
     // reach the stop index (too few nodes evaluated) is never accepted

@@ -31,7 +31,7 @@ struct TbLab {
 };
 inline TbLab tb_lab_args(void *ws, bool dry_run = false) {
     const bool debug = tune_get("RLVI_TJ_DEBUG", 0) != 0 && !dry_run;
-    return {debug ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF) : nullptr,
+    return {debug ? stamp_base(ws) : nullptr,
             tune_get("RLVI_TJ_VERIFY", 0)};
 }
 
@@ -207,7 +207,9 @@ __device__ __forceinline__ TbSolved trajb_solve(
     unsigned long long *__restrict__ dbg, PeerTable *__restrict__ pt = nullptr, const bool verify = false,
     float *__restrict__ red_out = nullptr, const double red_scale = 1.0) {
     int dbgi = 0;
-#define TB_STAMP() do { if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && dbgi < 60) dbg[dbgi++] = wall_clock64(); } while (0)
+    // who stamps and dumps (rlvi_stamps.h): thread 0 of the launch, workgroup 0 of the solve
+    const bool lab_t0 = RLVI_STAMPS && blockIdx.x == 0 && threadIdx.x == 0, lab_b0 = RLVI_STAMPS && b == 0;
+#define TB_STAMP() stamp_next<ST_SOLVE_SEQ>(dbg, lab_t0, dbgi)
     TB_STAMP();
     constexpr int TB_NW = TB_BLOCK / WAVE;
     static_assert(TB_NW >= TB_PER, "the stage-A gather needs four waves");
@@ -270,9 +272,8 @@ __device__ __forceinline__ TbSolved trajb_solve(
         }
     };
     stage_slice(true);
-#if RLVI_STAMPS
-    if (dbg != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { dbg[983] = __builtin_amdgcn_s_memtime(); dbg[985] = wall_clock64(); }
-#endif
+    stamp_cycles<ST_STAGED_CYCLES>(dbg, lab_t0);
+    stamp_clock<ST_STAGED_CLOCK>(dbg, lab_t0);
     // (node-split: the workgroup's minimum is known to every wave from here on -- each wave publishes the
     //  records of its own nodes itself, the minimum included)
     float wmin_all = __builtin_inff();
@@ -464,14 +465,16 @@ __device__ __forceinline__ TbSolved trajb_solve(
                         a3[q] = p3.x + p3.y; a4[q] = p4.x + p4.y;
                     }
                 }
-                if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) { dbg[980] = wall_clock64(); dbg[984] = __builtin_amdgcn_s_memtime(); }
+                // (spelled out, not lab_t0: a name of the enclosing function would be one more capture of this lambda)
+                stamp_clock<ST_SUMS_ARITH>(dbg, RLVI_STAMPS && blockIdx.x == 0 && threadIdx.x == 0 && round == 0);
+                stamp_cycles<ST_SUMS_CYCLES>(dbg, RLVI_STAMPS && blockIdx.x == 0 && threadIdx.x == 0 && round == 0);
                 const float tI = wave_reduce8(aI);
                 const float tP = wave_reduce8(aP);
                 const float tQ = wave_reduce8(aQ);
                 const float tD = wave_reduce8(aD);
                 float t3 = 0.0f, t4 = 0.0f;
                 if (HI) { t3 = wave_reduce8(a3); t4 = wave_reduce8(a4); }
-                if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) dbg[981] = wall_clock64();
+                stamp_clock<ST_SUMS_BFLY>(dbg, RLVI_STAMPS && blockIdx.x == 0 && threadIdx.x == 0 && round == 0);
                 // stage A straight from the registers: after the butterflies all eight lanes of a group hold
                 // their node's totals, so lane 8 s + j stores granule j of node c0 + s -- one write-through
                 // store per lane, no LDS, no workgroup barrier, and a wave's records leave as soon as THAT
@@ -524,7 +527,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
 #pragma unroll
                 for (int w = 1; w < TB_NW; ++w) wmin = fminf(wmin, sh.pmin[w]);
                 publish(rec + 4, tag, __float_as_uint(wmin));
-                if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && round == 0 && lane == 0) dbg[898] = __float_as_uint(wmin);
+                stamp_put<ST_SOLVE_WMIN>(dbg, lab_b0 && round == 0 && lane == 0, 0, (unsigned long long)__float_as_uint(wmin));
             }
             if (wave < 2 && nq > 5) {
                 float hq = 0.0f;
@@ -577,9 +580,9 @@ __device__ __forceinline__ TbSolved trajb_solve(
                 }
             }
             __syncthreads();
-            // (the reducer's combine on the stamps' axis, first round of workgroup 0: dbg[982] behind the barrier,
-            //  dbg[989] at the publish store)
-            if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) dbg[982] = wall_clock64();
+            // (the reducer's combine on the stamps' axis, first round of workgroup 0: RED_BARRIER behind the barrier,
+            //  RED_PUBLISH at the publish store)
+            stamp_clock<ST_RED_BARRIER>(dbg, lab_t0 && round == 0);
             if (wave == 0 && !dead && sh.out.dead == 0) {
                 // lane l stores granule l & 7 of replica l >> 3: one store per lane -- so it combines quantity
                 // l & 7 alone: the gathering waves' four partials in wave order from 0.0 (from +inf and by `<` for
@@ -634,10 +637,8 @@ __device__ __forceinline__ TbSolved trajb_solve(
                     }
                     val = (float)acc;
                 }
-                if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && round == 0) {
-                    asm volatile("" : "+v"(val));          // (the stamp is taken with the granule in hand)
-                    dbg[989] = wall_clock64();
-                }
+                if (RLVI_STAMPS) asm volatile("" : "+v"(val));          // (the stamp is taken with the granule in hand)
+                stamp_clock<ST_RED_PUBLISH>(dbg, lab_t0 && round == 0);
                 if (gq < nq && !xdead)
                     publish(B + ((size_t)(cl >> 3) * TJ_MAXK + b) * XCHG3_GRANULES + gq, tag, __float_as_uint(val));
             }
@@ -669,10 +670,10 @@ __device__ __forceinline__ TbSolved trajb_solve(
             }
             TB_STAMP();   // totals in
             const float gm = (lane < Ke && nq > 4) ? val[4] : __builtin_inff();
-            if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && round == 0) dbg[900 + lane] = ((unsigned long long)nq << 32) | __float_as_uint(val[4]);
+            stamp_put<ST_SOLVE_TOTALS_MIN>(dbg, lab_b0 && round == 0, lane, (unsigned)nq, __float_as_uint(val[4]));
             if (HI_OK && hi_round)      // (two workgroup barriers inside: the other waves meet them below)
-                tj_chain<true, true, HI_OK>(sh.out, Ke, K, val[0], val[1], val[2], val[3], gm, dead, rn_l, shift,
-                                            invN, tol, trace, true, xstep, dbg, val[5], val[6], false, split);
+                tj_chain<true, HI_OK>(sh.out, Ke, K, val[0], val[1], val[2], val[3], gm, dead, rn_l, shift,
+                                      invN, tol, trace, true, xstep, dbg, val[5], val[6], false, split);
             else if (round == 0)
                 tj_chain<true>(sh.out, Ke, K, val[0], val[1], val[2], val[3],
                                gm, dead,
@@ -682,7 +683,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
                                gm, dead,
                                 rn_l, shift, invN, tol, trace, true, xstep, dbg);
         } else if (HI_OK && hi_round) {
-            // The fourth-order first round: wave 0 is in tj_chain<true, true, true>, which passes two workgroup
+            // The fourth-order first round: wave 0 is in tj_chain<true, true>, which passes two workgroup
             // barriers -- behind its operand table and in front of its acceptance test.  Between them wave 1 runs
             // the half of that test that does not wait for the chain; every other wave, the caller's spare ones
             // included, passes the same two barriers.  hi_round is the same in every thread of the workgroup
@@ -701,8 +702,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
         r_fin = sh.out.res_rfin;
         const float delta = sh.out.res_delta;
         const bool found = sh.out.res_found != 0;
-        if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && tid == 0 && round < 24)
-            dbg[64 + round] = ((unsigned long long)((Ke << 8) | it) << 32) | __float_as_uint(delta);
+        stamp_put<ST_SOLVE_ROUNDS>(dbg, lab_b0 && tid == 0, round, (unsigned)((Ke << 8) | it), __float_as_uint(delta));
         rn_l = lane < K ? sh.out.nodes[lane] : 1.0f;
         if (lane == 0) rn_l = (float)(0.95 / (1.0 - 0.95));
         Ke = __builtin_amdgcn_readfirstlane(found ? round8(it + 2) : K);      // no stop index among the evaluated nodes: all of them
@@ -722,7 +722,7 @@ __device__ __forceinline__ TbSolved trajb_solve(
     if (!accepted && !dead && tid == 0) atomicOr(&hdr->status, RLVI_ST_NOCONV);
 
     TB_STAMP();   // solved
-    if ((RLVI_STAMPS && dbg != nullptr) && b == 0 && tid == 0) dbg[63] = (unsigned long long)dbgi;
+    stamp_put<ST_SOLVE_COUNT>(dbg, lab_b0 && tid == 0, 0, (unsigned long long)dbgi);
     if (b == 0 && tid < WAVE) {
         if (tid == 0) {
             if (out_iters != nullptr) *out_iters = it;

@@ -276,7 +276,7 @@ struct ThqShared {
     uint32_t lcount, lover, ltotal;    // key-list finish: this workgroup's keys inside the prefix / somebody's overflow / all keys
     uint32_t lkeys[THQ_LIST_CAP];
     uint32_t lall[THQ_LIST_ALL];       // the complete list (every workgroup's keys inside the prefix), dense
-    unsigned long long stamps[60];     // RLVI_THR_DEBUG only
+    unsigned long long stamps[stamp_count(ST_THR_SEQ)];     // RLVI_THR_DEBUG only
 };
 
 // 32-byte record = four granules (rlvi_coop.h): {count, min key, sum lo, sum hi}
@@ -293,7 +293,7 @@ __device__ __forceinline__ bool thq_load(gu64 *p, uint32_t tag, uint32_t &cnt, u
 // (identical on every workgroup).  All threads call; returns false after a timeout (sh.dead set).
 // Record r = half * 256 + bin lives at slot r of the stage-A row of its workgroup.
 // (stamps go to LDS and are copied out at the end: a global store in front of a barrier would cost its round trip)
-#define THQ_STAMP() do { if ((RLVI_STAMPS && dbg != nullptr) && blockIdx.x == 0 && threadIdx.x == 0 && dbgi < 60) sh.stamps[dbgi++] = wall_clock64(); } while (0)
+#define THQ_STAMP() stamp_next<ST_THR_SEQ>(dbg, RLVI_STAMPS && blockIdx.x == 0 && threadIdx.x == 0, dbgi, sh.stamps)
 // pt != nullptr (sharded over several GPUs): the bin's publishing wave first pushes this rank's totals
 // into every rank's inbox, adds up what all ranks pushed (integers: exact, order-free) and publishes the
 // global totals; ptag numbers the sharded exchanges of the group (rlvi_trajb.h uses the same counter).
@@ -860,10 +860,10 @@ __global__ __launch_bounds__(THQ_BLOCK) void threshold_radix_kernel(
         state->key = prefix;
         if (pt != nullptr) pt->dtag = ptag - 1u;
         state->valid = (ok && !all_inside) ? 1u : 0u;
-        if ((RLVI_STAMPS && dbg != nullptr)) {
-            for (int q = 0; q < dbgi; ++q) dbg[q] = sh.stamps[q];
-            dbg[63] = (unsigned long long)dbgi;
-        }
+        // (dbg is this kernel's first region of the slot table, not its base: see the launcher)
+        unsigned long long *tbl = stamp_table_of<ST_THR_SEQ>(dbg);
+        for (int q = 0; q < dbgi; ++q) stamp_put<ST_THR_SEQ>(tbl, true, q, sh.stamps[q]);
+        stamp_put<ST_THR_COUNT>(tbl, true, 0, (unsigned long long)dbgi);
         close_tags(hdr, tag);
     }
     if (hand_over && b == 0) {       // (nobody has written anything: every workgroup left at the first exchange)
@@ -900,8 +900,9 @@ static int launch_threshold(float *w, int64_t N, float alpha, float *thr, uint8_
     // entitled to (rlvi_threshold_sharded_check); nothing is launched, ws may be NULL
     const int64_t Nall = sharded ? n_all : N;
     PeerTable *pt = (sharded && !dry_run) ? reinterpret_cast<PeerTable *>(static_cast<char *>(ws) + WS_PEER_OFF) : nullptr;
+    // (lab stamps, rlvi_stamps.h: this kernel's region of the slot table -- the byte offset this launcher always passed)
     unsigned long long *dbg = (!dry_run && tune_get("RLVI_THR_DEBUG", 0))
-                                  ? reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF + 256)
+                                  ? stamp_region<ST_THR_SEQ>(stamp_base(ws))
                                   : nullptr;
     int rc = RLVI_E_LIMIT;
     bool launched = false;

@@ -99,9 +99,9 @@ class Workspace:
 
 
 def debug_scratch_offset():
-    """Byte offset of the workspace scratch area (where RLVI_TJ_DEBUG=1 leaves its stamps): the
-    fixed regions come first, so it is the size of a workspace for empty vectors minus its pad."""
-    return int(_lib.load().rlvi_workspace_bytes(0, 0)) - 256
+    """Byte offset of the workspace scratch area: the base of the slot table in which a stamps build run with
+    RLVI_TJ_DEBUG=1 / RLVI_THR_DEBUG=1 leaves its stamps (rlvi_amd/csrc/rlvi_stamps.h, tools/stamps.py)."""
+    return int(_lib.load().rlvi_workspace_region(b"scratch", None))
 
 
 def workspace(device, n=0, b=0):

@@ -2,13 +2,12 @@
 import os
 import sys
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import stamps  # noqa: E402
 from rlvi_amd import ops, synth  # noqa: E402
 
-SCRATCH_OFF = ops.debug_scratch_offset()
 dev = torch.device("cuda:0")
 for N in [int(a) for a in sys.argv[1:]]:
     for kind in ("bimodal", "ce", "heavy"):
@@ -27,7 +26,5 @@ for N in [int(a) for a in sys.argv[1:]]:
         cold = e0.elapsed_time(e1) * 1000 / 11
         rounds = ""
         if os.environ.get("RLVI_TJ_DEBUG"):
-            raw = wss[11].buf[SCRATCH_OFF:SCRATCH_OFF + 100 * 8].cpu().numpy().view(np.uint64)
-            rounds = " rounds(Ke,it,delta): " + str([(int(x >> 40), int((x >> 32) & 0xFF), round(float(
-                np.array([x & 0xFFFFFFFF], np.uint32).view(np.float32)[0]), 6)) for x in raw[64:76] if x])
+            rounds = " rounds(Ke,it,delta): " + str([(ke, it, round(d, 6)) for ke, it, d in stamps.rounds(stamps.read(wss[11]))[:12]])
         print(N, kind, "it", int(iters), "cold us/call %.1f" % cold, rounds, flush=True)

@@ -8,9 +8,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import stamps  # noqa: E402
 from rlvi_amd import ops, synth  # noqa: E402
-
-SCRATCH_OFF = ops.debug_scratch_offset()
 
 dev = torch.device("cuda:0")
 for N in [int(a) for a in sys.argv[1:]]:
@@ -36,26 +35,18 @@ for N in [int(a) for a in sys.argv[1:]]:
     print(N, "it", int(iters), "us/call %.1f" % (e0.elapsed_time(e1) * 1000 / 20), "status", ws.status(),
           flush=True)
     if os.environ.get("RLVI_TJ_DEBUG"):
-        raw = ws.buf[SCRATCH_OFF:SCRATCH_OFF + 700 * 8].cpu().numpy().view(np.uint64)
-        n = int(raw[63])
-        st = raw[:n].astype(np.int64)
-        print("   stamps us:", [round(float(x - st[0]) / 100.0, 2) for x in st][:24])
-        rd = raw[64:88]
-        print("   rounds (Ke, it, delta):",
-              [(int(x >> 40), int((x >> 32) & 0xFF),
-                float(np.array([x & 0xFFFFFFFF], np.uint32).view(np.float32)[0])) for x in rd if x][:12])
-        nn = raw[130:130 + 24]
-        rn = np.array(nn >> 32, np.uint32).view(np.float32).astype(np.float64)
-        rnew = np.array(nn & 0xFFFFFFFF, np.uint32).view(np.float32)
-        tot = raw[104:128].view(np.float64).reshape(8, 3)
+        S = stamps.read(ws)
+        print("   stamps us:", stamps.us(S.seq("SOLVE_SEQ", "SOLVE_COUNT"))[:24])
+        print("   rounds (Ke, it, delta):", stamps.rounds(S)[:12])
+        rn, rnew = S.f32_pair("TJ_NODES")
+        rn = rn.astype(np.float64)
+        tot = S.f64("TJ_TOTALS").reshape(8, 3)
         e = np.exp(-bufs[-1][0].cpu().numpy().astype(np.float64))
-        print("   scale", np.array([raw[103] & 0xFFFFFFFF], np.uint32).view(np.float32))
+        print("   scale", stamps.f32(stamps.lo(S["TJ_SCALE"])))
         for k in range(4):
             r = rn[k]
             print("   node", k, "rn", r, "rnew", rnew[k], "kernel S,P,Q", tot[k], "numpy S,P,Q",
                   np.sum(r * e / (1 + r * e)), np.sum(e / (1 + r * e) ** 2), np.sum(e * e / (1 + r * e) ** 3))
+        a, b = (v.astype(np.float64).reshape(-1, 64)[:, :24] for v in S.f32_pair("TJ_ROUND_NODES"))
         for xs in range(3):
-            nn = raw[400 + xs * 64:400 + xs * 64 + 24]
-            a = np.array(nn >> 32, np.uint32).view(np.float32).astype(np.float64)
-            b = np.array(nn & 0xFFFFFFFF, np.uint32).view(np.float32).astype(np.float64)
-            print("   round", xs, "rel change per node:", np.array2string(np.abs(b - a) / a, precision=2, max_line_width=250))
+            print("   round", xs, "rel change per node:", np.array2string(np.abs(b[xs] - a[xs]) / a[xs], precision=2, max_line_width=250))

@@ -128,77 +128,72 @@ with torch.cuda.stream(side):
     best = time_leg()
     extra = describe(best)
     if a.what in ("thr", "thr_fn") and any(t.startswith("RLVI_THR_DEBUG") for t in a.tune):
-        import numpy as np
-        off = ops.debug_scratch_offset() + 256
-        raw = ws.buf[off:off + 64 * 8].cpu().numpy().view(np.uint64)
-        n = int(raw[63])
-        st = raw[:n].astype(np.int64)
-        print("thr stamps (us since kernel start):", [round(float(x - st[0]) / 100.0, 2) for x in st])
+        import stamps
+        print("thr stamps (us since kernel start):", stamps.us(stamps.read(ws).seq("THR_SEQ", "THR_COUNT")))
     if os.environ.get("RLVI_TJ_DEBUG"):
-        import numpy as np
-        from rlvi_amd import _lib
-        off = ops.debug_scratch_offset()
-        raw = ws.buf[off:off + 240 * 8].cpu().numpy().view(np.uint64)
-        n = int(raw[63])
-        st = raw[:n].astype(np.int64)
-        print("stamps (us since kernel start):", [round(float(x - st[0]) / 100.0, 2) for x in st][:16])
+        import stamps
+        S = stamps.read(ws)
+        st = S.seq("SOLVE_SEQ", "SOLVE_COUNT")
+        t0 = int(st[0])
+
+        def at(name, i=0):       # a wall-clock stamp on the solve's axis: us since its first stamp
+            return stamps.us(S.word(name, i), t0)[0]
+        print("stamps (us since kernel start):", stamps.us(st)[:16])
         if a.what == "fused":
-            fs = ws.buf[off + 970 * 8:off + 978 * 8].cpu().numpy().view(np.uint64).astype(np.int64)
+            fs = S.ticks("FUSED_SEQ")
             print("fused stamps [start, tiles landed, rows done, barrier, solved, grad issued, -, out] us:",
-                  [round(float(x - fs[0]) / 100.0, 2) if x else None for x in fs], " solve starts at", round(float(st[0] - fs[0]) / 100.0, 2))
-        print('finite mask %x scale' % int(raw[102]), np.array([raw[103] & 0xFFFFFFFF], np.uint32).view(np.float32), 'totals lanes0-7 (S,P,D):', raw[104:128].view(np.float64).reshape(8,3))
-        print('round_ok', int(raw[128]), 'it', int(raw[129] >> 32), 'delta', np.array([raw[129] & 0xFFFFFFFF], np.uint32).view(np.float32))
-        nn = raw[130:130+44]
-        print('rn  :', np.array(nn >> 32, np.uint32).view(np.float32)[:44])
-        print('rnew:', np.array(nn & 0xFFFFFFFF, np.uint32).view(np.float32)[:44])
-        for xs in range(3):
-            rs = raw[200 + xs * 8: 200 + xs * 8 + 7].astype(np.int64)
-            print('  exchange', xs, '[stage1->, publish, polled, barrier, totals, chain, epilogue] us since kernel start:', [round(float(v - st[0]) / 100.0, 2) for v in rs])
-        rd = raw[64:88]
-        print('min, rfin:', np.array([raw[100] & 0xFFFFFFFF, raw[101] & 0xFFFFFFFF], np.uint32).view(np.float32))
-        full = ws.buf[off:off + 1000 * 8].cpu().numpy().view(np.uint64)
-        print("  wmin stored (wg0):", np.array([full[898] & 0xFFFFFFFF], np.uint32).view(np.float32), " totals val[4] lanes 0..3:", np.array(full[900:904] & 0xFFFFFFFF, np.uint32).view(np.float32), "nq", int(full[900] >> 32))
-        so = full[828:892]
-        print("  s_k    :", np.array(so >> 32, np.uint32).view(np.float32)[:24])
-        print("  rho_k  :", np.array(so & 0xFFFFFFFF, np.uint32).view(np.float32)[:24])
-        acc = full[699]
-        print("accept-without-verification:", int(acc >> 32), "it", int(acc & 0xFFFFFFFF))
-        eb = full[700:764]
-        print("  err_est:", np.array(eb >> 32, np.uint32).view(np.float32)[:24])
-        print("  band   :", np.array(eb & 0xFFFFFFFF, np.uint32).view(np.float32)[:24])
-        ee = full[764:828]
-        print("  E_k    :", np.array(ee >> 32, np.uint32).view(np.float32)[:24])
-        print("  slope  :", np.array(ee & 0xFFFFFFFF, np.uint32).view(np.float32)[:24])
-        cs = full[990:996].astype(np.int64)
-        print("recurrence wave [entry, prepared, chain, trust/tail, acceptance, out] us:", [round(float(v - cs[0]) / 100.0, 2) for v in cs])
-        if int(full[996]) > 0:      # (the split acceptance test: the helper wave between the recurrence wave's two barriers)
-            hs = full[996:999].astype(np.int64)
+                  [u if x else None for u, x in zip(stamps.us(fs), fs)], " solve starts at", stamps.us(t0, fs[0])[0])
+        print('finite mask %x scale' % S.word("TJ_FINITE"), stamps.f32(stamps.lo(S["TJ_SCALE"])), 'totals lanes0-7 (S,P,D):', S.f64("TJ_TOTALS").reshape(8, 3))
+        it, delta = S.pair("TJ_IT_DELTA")
+        print('round_ok', S.word("TJ_ROUND_OK"), 'it', int(it[0]), 'delta', stamps.f32(delta))
+        rn, rnew = S.f32_pair("TJ_NODES")
+        print('rn  :', rn[:44])
+        print('rnew:', rnew[:44])
+        nq, tmin = S.pair("SOLVE_TOTALS_MIN")
+        print("  wmin stored (wg0):", stamps.f32(stamps.lo(S["SOLVE_WMIN"])), " totals val[4] lanes 0..3:", stamps.f32(tmin[:4].copy()), "nq", int(nq[0]))
+        sk, rho = S.f32_pair("TJ_SK_RHO")
+        print("  s_k    :", sk[:24])
+        print("  rho_k  :", rho[:24])
+        acc, it_acc = S.pair("TJ_ACCEPT")
+        print("accept-without-verification:", int(acc[0]), "it", int(it_acc[0]))
+        err_est, band = S.f32_pair("TJ_ERR_BAND")
+        print("  err_est:", err_est[:24])
+        print("  band   :", band[:24])
+        ek, slope = S.f32_pair("TJ_EK_SLOPE")
+        print("  E_k    :", ek[:24])
+        print("  slope  :", slope[:24])
+        cs = S.ticks("CHAIN_SEQ")
+        print("recurrence wave [entry, prepared, chain, trust/tail, acceptance, out] us:", stamps.us(cs))
+        if S.word("HELPER") > 0:      # (the split acceptance test: the helper wave between the recurrence wave's two barriers)
             print("   helper wave [start, done] and the recurrence wave past its second barrier, us on the same axis:",
-                  [round(float(v - cs[0]) / 100.0, 2) for v in hs])
-        if int(full[982]) > 0 and int(full[989]) > 0:
-            print(f"reducer of node 0: behind its barrier at {(int(full[982]) - int(st[0])) / 100.0:.2f}, granule in hand at "
-                  f"{(int(full[989]) - int(st[0])) / 100.0:.2f} us since kernel start: combine {(int(full[989]) - int(full[982])) / 100.0:.2f} us")
-        # the kernel's entry on the stamps' axis: stamped as its first instruction (986 entry, 987 first data loads
-        # issued, 988 slice landed); a build without these has the kernel's length from its entry (961), taken at the
+                  stamps.us(list(S.ticks("HELPER")) + [S.word("CHAIN_BARRIER2")], cs[0]))
+        if S.word("RED_BARRIER") > 0 and S.word("RED_PUBLISH") > 0:
+            print(f"reducer of node 0: behind its barrier at {at('RED_BARRIER'):.2f}, granule in hand at "
+                  f"{at('RED_PUBLISH'):.2f} us since kernel start: combine {(S.word('RED_PUBLISH') - S.word('RED_BARRIER')) / 100.0:.2f} us")
+        # the kernel's entry on the stamps' axis: stamped as its first instruction (ENTRY: entry, first data loads
+        # issued, slice landed); a build without these has the kernel's length from its entry (KERNEL_TICKS), taken at the
         # last stamp, and its first two stamps sit behind the issue of the slice loads and behind their arrival
-        if int(full[986]) > 0:
-            e = [int(full[986 + k]) for k in range(3)]
-            print(f"kernel entry at {(e[0] - int(st[0])) / 100.0:.2f}, first data loads issued at {(e[1] - int(st[0])) / 100.0:.2f}, "
-                  f"slice landed at {(e[2] - int(st[0])) / 100.0:.2f} us on the stamps' axis: entry -> issued "
+        n, ticks = len(st), S.word("KERNEL_TICKS")
+        if S.word("ENTRY") > 0:
+            e = [int(x) for x in S.ticks("ENTRY")]
+            print(f"kernel entry at {at('ENTRY', 0):.2f}, first data loads issued at {at('ENTRY', 1):.2f}, "
+                  f"slice landed at {at('ENTRY', 2):.2f} us on the stamps' axis: entry -> issued "
                   f"{(e[1] - e[0]) / 100.0:.2f} us, entry -> slice landed {(e[2] - e[0]) / 100.0:.2f} us")
-        elif int(full[961]) > 0 and n > 1:
-            e0 = int(st[n - 1]) - int(full[961])
-            print(f"kernel entry (last stamp - kernel length) at {(e0 - int(st[0])) / 100.0:.2f} us on the stamps' axis: entry -> first "
-                  f"stamp (behind the issue of the slice loads) {(int(st[0]) - e0) / 100.0:.2f} us, entry -> slice landed "
+        elif ticks > 0 and n > 1:
+            e0 = int(st[n - 1]) - ticks
+            print(f"kernel entry (last stamp - kernel length) at {(e0 - t0) / 100.0:.2f} us on the stamps' axis: entry -> first "
+                  f"stamp (behind the issue of the slice loads) {(t0 - e0) / 100.0:.2f} us, entry -> slice landed "
                   f"(second stamp) {(int(st[1]) - e0) / 100.0:.2f} us")
-        if int(full[980]) > 0:
-            print("sums of workgroup 0 / wave 0: arithmetic done at", round(float(int(full[980]) - int(st[0])) / 100.0, 2),
-                  "butterflies done at", round(float(int(full[981]) - int(st[0])) / 100.0, 2), "us since kernel start")
-        if int(full[984]) > 0 and int(full[980]) > int(full[985]):
+        if S.word("SUMS_ARITH") > 0:
+            print("sums of workgroup 0 / wave 0: arithmetic done at", at("SUMS_ARITH"),
+                  "butterflies done at", at("SUMS_BFLY"), "us since kernel start")
+        if S.word("SUMS_CYCLES") > 0 and S.word("SUMS_ARITH") > S.word("STAGED_CLOCK"):
             print(f"   shader clock from the staged slice to the end of the sums' arithmetic: "
-                  f"{(int(full[984]) - int(full[983])) / (int(full[980]) - int(full[985])) * 0.1:.2f} GHz")
-        if int(full[961]) > 0:
-            print(f"shader clock in the E-step kernel: {int(full[960]) / int(full[961]) * 0.1:.2f} GHz "
-                  f"({int(full[960])} cycles in {int(full[961]) / 100.0:.2f} us)")
-        print("rounds (it, delta):", [(int(x >> 32), float(np.array([x & 0xFFFFFFFF], np.uint32).view(np.float32)[0])) for x in rd if x][:12])
+                  f"{(S.word('SUMS_CYCLES') - S.word('STAGED_CYCLES')) / (S.word('SUMS_ARITH') - S.word('STAGED_CLOCK')) * 0.1:.2f} GHz")
+        if ticks > 0:
+            cycles = S.word("KERNEL_CYCLES")
+            print(f"shader clock in the E-step kernel: {cycles / ticks * 0.1:.2f} GHz "
+                  f"({cycles} cycles in {ticks / 100.0:.2f} us)")
+        keit, delta = S.pair("SOLVE_ROUNDS")
+        print("rounds (it, delta):", [(int(k), float(d)) for k, d, x in zip(keit, stamps.f32(delta), S["SOLVE_ROUNDS"]) if x][:12])
     print(f"{a.tag or a.what:28s} B={B} C={C} N={N} {a.dtype}: {best:8.2f} us/launch{extra}  status={ws.status()}")
