@@ -489,6 +489,38 @@ int rlvi_linear_regression_f64(const double *X, const double *y, int64_t n, int6
                                int32_t *info, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The whole estimator logistic_regression(X, y, maxiter=100, tol=1e-2) of standard-learning/rlvi.py:92-108 as ONE
+ * launch (logreg.hip): weights = 1, fit, losses (:93-94), then up to `maxiter` times { update_weights(losses) with
+ * (estep_tol, estep_maxiter) = the reference's (1e-3, 100) (:98 -> :8-20), fit, losses (:101), stop when
+ * ||theta - prev|| / ||prev|| <= tol (:104-106) } -- decided on the device, the host waits once.
+ *   The fit replaces utils.sklearn_log_reg (standard-learning/utils.py:61-73: liblinear, L2, primal, C = 1e2, the
+ *   bias regularised, the weights divided by their maximum).  It returns the unique minimiser of
+ *       f(v) = 1/2 v.v + C sum_i (w_i / max w) log(1 + exp(-s_i z_i)),  v = (coef, bias), z = X coef + bias, s = 2y - 1,
+ *   which liblinear approximates to its tol = 1e-4: damped Newton from v = 0 (Hessian I + Z^T diag(.) Z as a weighted
+ *   Gram matrix of [X | 1] on the fp64 matrix cores, L D L^T on one wave, Armijo halving), until
+ *   ||g|| <= 1e-12 ||g(0)|| or a full step no longer lowers f; at most 50 Newton steps per fit.
+ *   The losses are the reference's own (utils.py:62-64): -log p(class 0 | x) = log(1 + exp(z)) for EVERY sample.
+ *   X [n, d] row-major, y [n] of 0.0 / 1.0; C > 0 (the reference: 1e2).
+ *   theta [d + 1] = (intercept, coef ...) as utils.py:69, weights [n] (the final pi), losses [n] (of the last fit; may
+ *   be NULL), info int32[4] = { outer iterations, inner iterations of the last E-step, Newton steps in all, flag } --
+ *   all device pointers.  flag 1: data that is not finite, a y that is neither 0 nor 1, weights without a positive
+ *   one, or a pivot that is not safely positive -- theta / weights / losses are then NOT written.  flag 2: a fit took
+ *   its 50 Newton steps without meeting the stop test, or its 40 Armijo halvings found no acceptable step away from
+ *   the rounding floor; RLVI_ST_NOCONV is raised in the workspace, the results are those of the last accepted step.
+ * LIMITS: n <= 4096 (one workgroup, 16 samples per thread) and d <= 30 ([X | 1] and the gradient's column fill two
+ * 16-column blocks); rlvi_logistic_regression_check says 0 / RLVI_E_LIMIT (RLVI_E_SHAPE for n or d <= 0) without
+ * launching.
+ * rlvi_logistic_fit_f64: ONE fit and its losses for the caller's weights w [n] (>= 0, one of them > 0) -- the
+ * M-step on its own (utils.py:61-73), the same device code; info = { 0, 0, Newton steps, flag }.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_logistic_regression_check(int64_t n, int64_t d);
+int rlvi_logistic_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter, double tol,
+                                 double estep_tol, int estep_maxiter, double C, double *theta, double *weights,
+                                 double *losses, int32_t *info, void *ws, void *stream);
+int rlvi_logistic_fit_f64(const double *X, const double *y, const double *w, int64_t n, int64_t d, double C,
+                          double *theta, double *losses, int32_t *info, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

@@ -90,6 +90,10 @@ SIGNATURES = {
     "rlvi_logistic_nll_f64": (_int, [_vp, _vp, _f64, _i64, _i64, _vp, _vp]),
     "rlvi_linear_regression_check": (_int, [_i64, _i64]),
     "rlvi_linear_regression_f64": (_int, [_vp, _vp, _i64, _i64, _int, _f64, _f64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "rlvi_logistic_regression_check": (_int, [_i64, _i64]),
+    "rlvi_logistic_regression_f64": (_int, [_vp, _vp, _i64, _i64, _int, _f64, _f64, _int, _f64, _vp, _vp, _vp, _vp,
+                                            _vp, _vp]),
+    "rlvi_logistic_fit_f64": (_int, [_vp, _vp, _vp, _i64, _i64, _f64, _vp, _vp, _vp, _vp, _vp]),
     "rlvi_sample_weight_online_f64": (_int, [_vp, _vp, _f64, _int, _i64, _i64, _f64, _int, _vp, _vp, _vp, _vp]),
     "rlvi_stream_copy": (_int, [_vp, _vp, ctypes.c_size_t, _vp]),
 }
@@ -108,7 +112,8 @@ _ST_TEXT = {
     ST_RANGE: "a label or sample index was out of range (the reference raises an IndexError there)",
     ST_TIMEOUT: "an inter-workgroup wait timed out: the cooperating workgroups were not all resident "
                 "(another process on this GPU?); pi / threshold were left as they were",
-    ST_NOCONV: "the E-step did not reach its fixed point (non-finite residuals?)",
+    ST_NOCONV: "the E-step did not reach its fixed point (non-finite residuals?), or a logistic fit did not meet "
+               "its stop test within its Newton steps",
     ST_SINGULAR: "weighted least squares: the Gram matrix is not positive definite",
 }
 

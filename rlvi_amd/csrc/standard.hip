@@ -25,58 +25,13 @@
 // Sums are fp64 in a fixed order: same inputs, same bits.
 #include <string.h>
 
-#include "rlvi_common.h"
+#include "rlvi_sl.h"
 
 namespace rlvi {
 
-typedef double sd4_t __attribute__((ext_vector_type(4)));
-
-// (four waves, one per SIMD: a reduction of the fixed point costs every WAVE ~80 instructions whatever it holds, and
-//  two waves on a SIMD take turns at its issue slots -- eight waves with two samples per thread measured 0.79 us per
-//  inner iteration)
-constexpr int SL_THREADS = 256;
-constexpr int SL_NW = SL_THREADS / WAVE;
-constexpr int SL_DP = 32;                         // [X | y] padded to two 16-column blocks: d <= 31
 constexpr int SL_XS = 64;                          // 4-row k-panels a wave keeps in registers (resident design: n <= 1024)
 constexpr int SL_RU = 4;                           // 16-row blocks of the residual pass in flight per wave and trip
 constexpr int SL_GU = 16;                          // 4-row k-panels of the Gram loop in flight per wave and trip
-constexpr int SL_MAXN = 4096;                     // samples the one-workgroup form takes (16 per thread)
-constexpr int SL_GPITCH = SL_DP + 1;
-
-// 1 / x to working precision: v_rcp_f64 + two Newton steps (the factorisation's pivots; not correctly rounded,
-// 1e-16 relative, and a tenth of the IEEE division's instruction count on a wave that issues alone)
-__device__ __forceinline__ double sl_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-    return r;
-}
-// the value is needed HERE, whatever later selects do with it: keeps the compiler from sinking a load into the
-// branch of the select that consumes it (a load under a branch is waited for before the next one is issued)
-__device__ __forceinline__ void sl_keep(double &v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ double sl_readlane(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(unsigned)(b & 0xFFFFFFFFll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// {a, b} summed over the workgroup, every thread gets the totals: wave butterflies, one slot pair per wave in
-// `slots` (two parities x SL_NW x 2 doubles), ONE barrier; the slots of parity p are not written again before
-// everybody has passed the NEXT barrier, i.e. has read them.
-__device__ __forceinline__ void sl_block_sum2(double &a, double &b, double *slots, int &parity) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    a = wave_sum(a);
-    b = wave_sum(b);
-    double *s = slots + (size_t)parity * SL_NW * 2;
-    if (lane == 0) { s[2 * wave] = a; s[2 * wave + 1] = b; }
-    __syncthreads();
-    double ta = 0.0, tb = 0.0;
-#pragma unroll
-    for (int w = 0; w < SL_NW; ++w) { ta += s[2 * w]; tb += s[2 * w + 1]; }
-    a = ta; b = tb;
-    parity ^= 1;
-}
 
 // lab build (-DRLVI_STAMPS=1, tools/build_variants.py): thread 0 leaves 100 MHz wall-clock stamps of the phases in
 // the workspace scratch (tools/lab/linreg_phases.py prints them); compiled out of the product library
@@ -227,6 +182,8 @@ __device__ __forceinline__ bool sl_wls(const SlShared &sh, const double *__restr
     __syncthreads();
     SL_STAMP();   // block sums done
     // ---- wave 0: G = L D L^T, row t of the lower triangle in lane t's registers
+    // (the same code as sl_ldlt_solve of rlvi_sl.h, which logreg.hip calls: kept in place here because calling it moves
+    //  this kernel's register allocation -- a change to either copy belongs in both)
     if (wave == 0) {
         int t = lane & (SL_DP - 1);
         // (opaque: the lane masks t > j, t == j below are loop-invariant across the estimator's outer loop, and
@@ -496,6 +453,8 @@ __global__ __launch_bounds__(SL_THREADS) void linreg_rlvi_kernel(
             e[j] = v ? exp(-(sh.rsh[v ? q : 0] * hs)) : 0.0;      // losses = 0.5 r / sigma2 (rlvi.py:74); exp(-losses)
             w[j] = v ? 0.95 : 0.0;                                 // rlvi.py:10
         }
+        // (the same loop as sl_estep_fixed_point of rlvi_sl.h: in place here for the same reason as the factorisation
+        //  in sl_wls -- a change to either copy belongs in both)
         double ratio;
         { const double eps = 1.0 - 0.95; ratio = eps / (1.0 - eps); }
         int it = 0;

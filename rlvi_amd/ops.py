@@ -559,6 +559,63 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter
     return theta, weights, info
 
 
+def logistic_regression_check(n, d):
+    """True if rlvi_logistic_regression_f64 / rlvi_logistic_fit_f64 take an [n, d] design (n <= 4096, d <= 30)."""
+    return _lib.load().rlvi_logistic_regression_check(int(n), int(d)) == 0
+
+
+def _logistic_inputs(X, *vectors):
+    _require_gpu(X, *vectors)
+    if X.dim() != 2 or X.dtype != torch.float64 or not X.is_contiguous():
+        raise ValueError("X [n, d] must be a contiguous fp64 device tensor")
+    for v in vectors:
+        if v.dtype != torch.float64 or not v.is_contiguous() or v.numel() != X.shape[0]:
+            raise ValueError("y and the weights must be contiguous fp64 device tensors of X's n elements")
+    return X.shape
+
+
+def logistic_fit(X, y, w, C=100.0, theta=None, losses=None, info=None, ws=None):
+    """utils.sklearn_log_reg(X, y, weights) of standard-learning/utils.py:61-73 as ONE launch on device tensors
+    (rlvi_logistic_fit_f64; no host synchronisation here): the minimiser of 1/2 v.v + C sum (w_i / max w)
+    log(1 + exp(-s_i z_i)) that liblinear approximates, by Newton to the rounding floor.  Returns (theta [d + 1] =
+    (intercept, coef), losses [n] = log(1 + exp(z)), info int32[4] = {0, 0, Newton steps, flag}); flag 1: nothing
+    was written (data not finite, y not 0 / 1, no positive weight, a pivot not safely positive); flag 2: the Newton cap, or a line search
+    without an acceptable step (RLVI_ST_NOCONV in ws)."""
+    L = _lib.load()
+    n, d = _logistic_inputs(X, y, w)
+    if theta is None:
+        theta = torch.empty(d + 1, dtype=torch.float64, device=X.device)
+    if losses is None:
+        losses = torch.empty(n, dtype=torch.float64, device=X.device)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=X.device)
+    ws = ws or workspace(X.device, n, 0)
+    _lib.check(L.rlvi_logistic_fit_f64(_ptr(X), _ptr(y), _ptr(w), n, d, float(C), _ptr(theta), _ptr(losses),
+                                       _ptr(info), ws.ptr, _stream_ptr()), "rlvi_logistic_fit_f64")
+    return theta, losses, info
+
+
+def logistic_regression(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, C=100.0, theta=None,
+                        weights=None, losses=None, info=None, ws=None):
+    """logistic_regression(X, y, maxiter, tol) of standard-learning/rlvi.py:92-108 as ONE launch on device tensors
+    (rlvi_logistic_regression_f64; no host synchronisation here).  Returns (theta [d + 1] = (intercept, coef),
+    weights [n], info int32[4] = {outer iterations, inner iterations of the last E-step, Newton steps in all, flag});
+    `losses` [n], if given, receives the last fit's.  flag as logistic_fit."""
+    L = _lib.load()
+    n, d = _logistic_inputs(X, y)
+    if theta is None:
+        theta = torch.empty(d + 1, dtype=torch.float64, device=X.device)
+    if weights is None:
+        weights = torch.empty(n, dtype=torch.float64, device=X.device)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=X.device)
+    ws = ws or workspace(X.device, n, 0)
+    _lib.check(L.rlvi_logistic_regression_f64(_ptr(X), _ptr(y), n, d, int(maxiter), float(tol), float(estep_tol),
+                                              int(estep_maxiter), float(C), _ptr(theta), _ptr(weights), _ptr(losses),
+                                              _ptr(info), ws.ptr, _stream_ptr()), "rlvi_logistic_regression_f64")
+    return theta, weights, info
+
+
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,
                          iters=None):
     """One mini-batch of online-learning/main.py:293-297 in ONE launch on device tensors: residuals =

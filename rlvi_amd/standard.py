@@ -9,7 +9,8 @@
 The E-step fixed point and the per-sample NLL (the X.theta contraction) run in
 librlvi_gfx950.so, and so does the weighted least-squares solve of linear_regression (normal
 equations on the fp64 MFMA units + Cholesky); logistic regression keeps sklearn's liblinear on
-the host, as the reference has it.
+the host by default, as the reference has it, and runs as one launch of its own Newton solver
+with solver="newton" (logreg.hip).
 Host arrays cross PCIe once per call; use rlvi_amd.ops directly to keep data resident.
 """
 import numpy as np
@@ -177,7 +178,60 @@ def _sklearn_log_reg(X_host, y_host, X_dev, w_dev, reg_coeff=1e2):
     return theta, losses
 
 
-def logistic_regression(X, y, maxiter=100, tol=1e-2):
+def _logistic_regression_newton(X, y, maxiter, tol, return_info):
+    """solver="newton": one pinned H2D copy of [X | y], ONE launch (rlvi_logistic_regression_f64), one pinned D2H
+    copy of {theta, weights, info}, one host wait."""
+    Xh = np.ascontiguousarray(X, dtype=np.float64)
+    yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
+        raise ValueError("X must be [n, d] and y [n]")
+    n, d = Xh.shape
+    # what sklearn's fit raises a ValueError for, before anything reaches the device
+    if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
+        raise ValueError("Input contains NaN or infinity.")
+    if not np.isin(yh, (0.0, 1.0)).all():
+        raise ValueError("y must hold the class labels 0 and 1")
+    if n == 0 or yh.min() == yh.max():
+        raise ValueError("This solver needs samples of at least 2 classes in the data")
+    if d == 0 or not ops.logistic_regression_check(n, d):
+        raise _lib.RlviError(f"logistic_regression(solver='newton') takes n <= 4096 samples and 1 <= d <= 30 features "
+                             f"in its one launch: got n = {n}, d = {d} (solver='liblinear' has no such limit)")
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    D = d + 1
+    h_in, h_out, d_in, d_out = _STAGE.get(dev, "logreg", (n * d + n, D + n + 2), device_side=True)
+    h_in.numpy()[:n * d] = Xh.reshape(-1)
+    h_in.numpy()[n * d:] = yh
+    d_in.copy_(h_in, non_blocking=True)
+    info = d_out[D + n:].view(torch.int32)                  # 4 x int32 behind theta and the weights
+    ops.logistic_regression(d_in[:n * d].view(n, d), d_in[n * d:], maxiter=maxiter, tol=tol, theta=d_out[:D],
+                            weights=d_out[D:D + n], info=info, ws=ws)
+    h_out.copy_(d_out, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()            # the one host wait of the call
+    res = h_out.numpy()
+    inf = res[D + n:].view(np.int32)
+    if inf[3] == 1:
+        raise ValueError("logistic_regression: the fit met numbers that are not finite, or a pivot of its Newton "
+                         "system that is not safely positive (a design scaled beyond what fp64 resolves)")
+    if inf[3] == 2:
+        ws.raise_on_status("logistic_regression", mask=_lib.ST_NOCONV)
+    if return_info:
+        return res[:D].copy(), res[D:D + n].copy(), int(inf[0])
+    return res[:D].copy()
+
+
+def logistic_regression(X, y, maxiter=100, tol=1e-2, *, solver="liblinear", return_info=False):
+    """rlvi.py:92-108.  solver="liblinear" (the default): sklearn's liblinear on the host once per outer iteration,
+    as the reference has it.  solver="newton": the whole estimator in ONE launch (n <= 4096, d <= 30, RlviError
+    beyond; never a silent change of solver) -- each fit is the minimiser liblinear approximates to its tol = 1e-4,
+    so theta agrees with the default's to about 1e-5 relative, not to the bit.  return_info (solver="newton"):
+    (theta, weights, outer iterations)."""
+    if solver == "newton":
+        return _logistic_regression_newton(X, y, maxiter, tol, return_info)
+    if solver != "liblinear":
+        raise ValueError(f"unknown solver {solver!r}: 'liblinear' or 'newton'")
+    if return_info:
+        raise ValueError("return_info needs solver='newton'")
     dev = _dev()
     Xh = np.ascontiguousarray(X, dtype=np.float64)
     yh = np.asarray(y)
