@@ -521,6 +521,52 @@ int rlvi_logistic_fit_f64(const double *X, const double *y, const double *w, int
                           double *theta, double *losses, int32_t *info, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The estimators mean, pca and covariance of standard-learning/rlvi.py as ONE launch each (moments.hip), and the
+ * constrained E-step on its own.  One persistent workgroup; the sample [n, d] row-major is staged into LDS once;
+ * weighted moments in two passes (sums, then the second moment about the mean just found), fp64 in a fixed order:
+ * the same inputs give the same bits.  Every stop decision is taken on the device, the host waits once.
+ *   mean        rlvi.py:46-65: weights = 1, theta = sum w x / sum w, r = ||theta - x||^2, sigma2 = sum w r / sum w,
+ *               losses = 1/2 r / sigma2 (:47-51), then up to `maxiter` times { update_weights(losses) with
+ *               (estep_tol, estep_maxiter) = the reference's (1e-3, 100) (:54 -> :8-20), theta and losses again
+ *               (:56-59), stop when ||theta - prev|| / ||prev|| <= tol (:61-63) }.  theta [d].
+ *   pca         rlvi.py:111-125 with utils.py:76-89: the fit is the first principal component of the rows w x
+ *               (centred by their plain column mean; the eigenvector of the largest eigenvalue of their d x d scatter
+ *               matrix by cyclic Jacobi sweeps, at most 30; normalised; the component of largest magnitude -- the
+ *               first on a tie -- positive, which is sklearn's svd_flip), losses = ||x||^2 - (x.theta)^2 on the
+ *               uncentred rows.  theta_init [d] or NULL: replaces the FIRST fit and is used as is, not normalised
+ *               (utils.py:81-88).  d = 1 gives theta = [1].  An exactly repeated largest eigenvalue leaves the
+ *               direction unpinned.  theta [d].
+ *   covariance  rlvi.py:128-144 with utils.py:92-108: mu = sum w x / sum w, C = sum w (x - mu)(x - mu)^T / sum w,
+ *               losses = 1/2 ((x - mu)^T C^-1 (x - mu) + log det C + d log 2 pi) by an L D L^T factorisation; the
+ *               E-step is update_weights_constrained (below) with n_eff (the reference: n (1 - eps));
+ *               Frobenius norms in the stop test.  theta [d * d] row-major.  Requires 0 < n_eff < n.
+ *   rlvi_update_weights_constrained_f64   rlvi.py:23-43: update_weights(losses, tol, maxiter) first; if its weights
+ *               sum to less than n_eff, out_i = 1 / (1 + c exp(l_i - s)), c = (n - n_eff) / n_eff, with the shift s
+ *               at which they sum to n_eff -- the exact root (safeguarded Newton on the bracket [min l, max l],
+ *               at most 200 evaluations) of what the reference hands to scipy's minimize_scalar as a square: the
+ *               contract is the root, not Brent's iterate.  n <= 4096.
+ *               info = { root-find evaluations, the fixed point's iterations, 1 if the constraint was active, flag }.
+ * weights [n] (the final pi), info int32[4] = { outer iterations, inner iterations of the last E-step, count, flag },
+ * count = mean: inner iterations in all; pca: Jacobi sweeps in all; covariance: E-steps in which the constraint was
+ * active -- all device pointers.  flag 1: data that is not finite, no positive weight, a variance or a pivot that is
+ * not safely positive, n_eff outside (0, n): NOTHING is written.  flag 2: the Jacobi cap or the root-find cap was
+ * hit; RLVI_ST_NOCONV is raised in the workspace and the last iterate is returned.
+ * LIMITS: 2 <= n <= 4096, 1 <= d <= 8 and n d <= 16 384 (the sample resident in 128 KB of LDS); rlvi_moments_check
+ * says 0 / RLVI_E_LIMIT (RLVI_E_SHAPE for n or d <= 0) without launching.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_moments_check(int64_t n, int64_t d);
+int rlvi_robust_mean_f64(const double *sample, int64_t n, int64_t d, int maxiter, double tol, double estep_tol,
+                         int estep_maxiter, double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_robust_pca_f64(const double *sample, int64_t n, int64_t d, int maxiter, double tol,
+                        const double *theta_init, double estep_tol, int estep_maxiter, double *theta,
+                        double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_robust_covariance_f64(const double *sample, int64_t n, int64_t d, double n_eff, int maxiter, double tol,
+                               double estep_tol, int estep_maxiter, double *theta, double *weights, int32_t *info,
+                               void *ws, void *stream);
+int rlvi_update_weights_constrained_f64(const double *losses, int64_t n, double n_eff, double tol, int maxiter,
+                                        double *out, int32_t *info, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

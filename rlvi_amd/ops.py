@@ -616,6 +616,89 @@ def logistic_regression(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxit
     return theta, weights, info
 
 
+def moments_check(n, d):
+    """True if rlvi_robust_mean_f64 / _pca_f64 / _covariance_f64 take an [n, d] sample (2 <= n <= 4096, 1 <= d <= 8,
+    n d <= 16 384: the sample is resident in LDS)."""
+    return _lib.load().rlvi_moments_check(int(n), int(d)) == 0
+
+
+def _moments_call(entry, sample, theta_numel, theta, weights, info, ws, args):
+    L = _lib.load()
+    _require_gpu(sample)
+    if sample.dim() != 2 or sample.dtype != torch.float64 or not sample.is_contiguous():
+        raise ValueError("sample [n, d] must be a contiguous fp64 device tensor")
+    n, d = sample.shape
+    if theta is None:
+        theta = torch.empty(theta_numel(d), dtype=torch.float64, device=sample.device)
+    if weights is None:
+        weights = torch.empty(n, dtype=torch.float64, device=sample.device)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=sample.device)
+    ws = ws or workspace(sample.device, n, 0)
+    _lib.check(getattr(L, entry)(_ptr(sample), n, d, *args, _ptr(theta), _ptr(weights), _ptr(info), ws.ptr,
+                                 _stream_ptr()), entry)
+    return theta, weights, info
+
+
+def robust_mean(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None, info=None,
+                ws=None):
+    """mean(sample, maxiter, tol) of standard-learning/rlvi.py:46-65 as ONE launch on device tensors
+    (rlvi_robust_mean_f64; no host synchronisation here).  Returns (theta [d], weights [n], info int32[4] = {outer
+    iterations, inner iterations of the last E-step, inner iterations in all, flag}); flag 1: nothing was written
+    (data not finite, a variance not safely positive)."""
+    return _moments_call("rlvi_robust_mean_f64", sample, lambda d: d, theta, weights, info, ws,
+                         (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)))
+
+
+def robust_pca(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, estep_maxiter=100, theta=None,
+               weights=None, info=None, ws=None):
+    """pca(sample, maxiter, tol, theta_init) of standard-learning/rlvi.py:111-125 as ONE launch on device tensors
+    (rlvi_robust_pca_f64).  theta_init [d] (fp64, on the device) replaces the first fit and is used as is.  Returns
+    (theta [d], weights [n], info = {outer, inner of the last E-step, Jacobi sweeps in all, flag}); flag 2: an
+    eigen-solve hit its 30 sweeps (RLVI_ST_NOCONV in ws)."""
+    if theta_init is not None:
+        _require_gpu(theta_init)
+        if theta_init.dtype != torch.float64 or not theta_init.is_contiguous() or theta_init.numel() != sample.shape[1]:
+            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
+    return _moments_call("rlvi_robust_pca_f64", sample, lambda d: d, theta, weights, info, ws,
+                         (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)))
+
+
+def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, theta=None,
+                      weights=None, info=None, ws=None):
+    """covariance(sample, eps, maxiter, tol) of standard-learning/rlvi.py:128-144 with n_eff = n (1 - eps) as ONE
+    launch on device tensors (rlvi_robust_covariance_f64).  Returns (theta [d, d], weights [n], info = {outer, inner
+    of the last E-step, E-steps with the constraint active, flag}); flag 1: nothing was written (data not finite, a
+    pivot not safely positive, n_eff outside (0, n)); flag 2: a root-find hit its cap (RLVI_ST_NOCONV in ws)."""
+    theta, weights, info = _moments_call("rlvi_robust_covariance_f64", sample,
+                                         lambda d: d * d, None if theta is None else theta.view(-1), weights, info, ws,
+                                         (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)))
+    d = sample.shape[1]
+    return theta.view(d, d), weights, info
+
+
+def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, info=None, ws=None):
+    """update_weights_constrained(losses, n_eff, tol, maxiter) of standard-learning/rlvi.py:23-43 as ONE launch on a
+    device tensor of n <= 4096 losses (rlvi_update_weights_constrained_f64): the plain fixed point, then, if its
+    weights sum to less than n_eff, the weights 1 / (1 + c exp(l - s)) at the exact root s of their sum = n_eff.
+    Returns (weights [n], info int32[4] = {root-find evaluations, the fixed point's iterations, 1 if the constraint
+    was active, flag})."""
+    L = _lib.load()
+    _require_gpu(losses)
+    if losses.dim() != 1 or losses.dtype != torch.float64 or not losses.is_contiguous():
+        raise ValueError("losses [n] must be a contiguous fp64 device tensor")
+    n = losses.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=losses.device)
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=losses.device)
+    ws = ws or workspace(losses.device, n, 0)
+    _lib.check(L.rlvi_update_weights_constrained_f64(_ptr(losses), n, float(n_eff), float(tol), int(maxiter), _ptr(out),
+                                                     _ptr(info), ws.ptr, _stream_ptr()),
+               "rlvi_update_weights_constrained_f64")
+    return out, info
+
+
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,
                          iters=None):
     """One mini-batch of online-learning/main.py:293-297 in ONE launch on device tensors: residuals =

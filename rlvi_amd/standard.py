@@ -3,6 +3,7 @@
     update_weights(losses, tol=1e-3, maxiter=100)             reference rlvi.py:8-20
     update_weights_constrained(losses, n_eff, ...)            reference rlvi.py:23-43
     mean / pca / covariance                                    reference rlvi.py:46-65, :111-144
+                                                               (one_launch=True: one launch each, moments.hip)
     linear_regression(X, y, maxiter=100, tol=1e-3) -> theta    reference rlvi.py:68-89
     logistic_regression(X, y, maxiter=100, tol=1e-2) -> theta  reference rlvi.py:92-108
 
@@ -248,9 +249,9 @@ def logistic_regression(X, y, maxiter=100, tol=1e-2, *, solver="liblinear", retu
 
 
 # ---- the remaining estimators of standard-learning/rlvi.py on the same GPU E-step.
-# n is tens to hundreds here: the E-step runs in librlvi_gfx950.so, the small dense algebra around
+# n is tens to hundreds here: by default the E-step runs in librlvi_gfx950.so, the small dense algebra around
 # it (weighted means, a 2x2 SVD / solve, scipy's 1-D KKT solve) stays on the host as numpy, exactly
-# where the reference has it.
+# where the reference has it; one_launch=True runs the whole estimator as ONE launch (moments.hip).
 def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100):
     """rlvi.py:23-43."""
     from scipy import optimize as opt
@@ -271,8 +272,71 @@ def _gauss_losses(sample, theta, w):
     return 0.5 * r / (w @ r / np.sum(w))
 
 
-def mean(sample, maxiter=100, tol=1e-3):
-    """rlvi.py:46-65."""
+def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None):
+    """one_launch=True of mean / pca / covariance: one pinned H2D copy of the sample (and theta_init), ONE launch
+    (rlvi_robust_mean_f64 / _pca_f64 / _covariance_f64), one pinned D2H copy of {theta, weights, info}, one host
+    wait."""
+    xh = np.ascontiguousarray(sample, dtype=np.float64)
+    if xh.ndim != 2:
+        raise ValueError("sample must be [n, d]")
+    n, d = xh.shape
+    init = None if theta_init is None else np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
+    if init is not None and init.shape[0] != d:
+        raise ValueError("theta_init must have the sample's d elements")
+    # before anything reaches the device
+    if not np.isfinite(xh).all() or (init is not None and not np.isfinite(init).all()):
+        raise ValueError("Input contains NaN or infinity.")
+    if kind == "covariance" and not 0.0 < eps < 1.0:
+        raise ValueError(f"covariance(one_launch=True) needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
+    if n == 0 or d == 0 or not ops.moments_check(n, d):
+        raise _lib.RlviError(f"{kind}(one_launch=True) takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with "
+                             f"n d <= 16384 in its one launch: got n = {n}, d = {d} (one_launch=False has no such "
+                             f"limit)")
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    nt = d * d if kind == "covariance" else d
+    h_in, h_out, d_in, d_out = _STAGE.get(dev, "moments_" + kind, (n * d + d, nt + n + 2), device_side=True)
+    h_in.numpy()[:n * d] = xh.reshape(-1)
+    if init is not None:
+        h_in.numpy()[n * d:] = init
+    d_in.copy_(h_in, non_blocking=True)
+    x_dev = d_in[:n * d].view(n, d)
+    out = dict(theta=d_out[:nt], weights=d_out[nt:nt + n], info=d_out[nt + n:].view(torch.int32), ws=ws)
+    if kind == "mean":
+        ops.robust_mean(x_dev, maxiter=maxiter, tol=tol, **out)
+    elif kind == "pca":
+        ops.robust_pca(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else d_in[n * d:], **out)
+    else:
+        ops.robust_covariance(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, **out)
+    h_out.copy_(d_out, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()            # the one host wait of the call
+    res = h_out.numpy()
+    inf = res[nt + n:].view(np.int32).copy()
+    if inf[3] == 1:
+        if kind == "covariance":
+            raise ValueError("Singular covariance matrix")   # utils.py:99-100
+        raise ValueError(f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely "
+                         f"positive")
+    if inf[3] == 2:
+        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
+    theta = res[:nt].copy().reshape((d, d) if kind == "covariance" else (d,))
+    if return_info:
+        return theta, res[nt:nt + n].copy(), inf
+    return theta
+
+
+def _host_loop_only(one_launch, return_info):
+    if return_info and not one_launch:
+        raise ValueError("return_info needs one_launch=True")
+
+
+def mean(sample, maxiter=100, tol=1e-3, *, one_launch=False, return_info=False):
+    """rlvi.py:46-65.  one_launch=True: the whole estimator in ONE launch (2 <= n <= 4096, d <= 8, n d <= 16384,
+    RlviError beyond; never a silent change of path); return_info: (theta, weights, info int32[4] = {outer
+    iterations, inner iterations of the last E-step, inner iterations in all, flag})."""
+    _host_loop_only(one_launch, return_info)
+    if one_launch:
+        return _moments_one_launch("mean", sample, maxiter, tol, return_info)
     sample = np.asarray(sample, np.float64)
     w = np.ones(sample.shape[0])
     theta = w @ sample / np.sum(w)
@@ -299,11 +363,20 @@ def _pca_step(sample, w):
     return theta, np.sum(sample ** 2, axis=1) - (sample @ theta) ** 2
 
 
-def pca(sample, maxiter=100, tol=1e-2):
-    """rlvi.py:111-125 (theta_init=None)."""
+def pca(sample, maxiter=100, tol=1e-2, theta_init=None, *, one_launch=False, return_info=False):
+    """rlvi.py:111-125.  theta_init replaces the first fit and is used as is, not normalised (utils.py:81-88).
+    one_launch=True: the whole estimator in ONE launch (limits and return_info as for mean; info[2]: Jacobi sweeps in
+    all)."""
+    _host_loop_only(one_launch, return_info)
+    if one_launch:
+        return _moments_one_launch("pca", sample, maxiter, tol, return_info, theta_init=theta_init)
     sample = np.asarray(sample, np.float64)
     w = np.ones(sample.shape[0])
-    theta, losses = _pca_step(sample, w)
+    if theta_init is None:
+        theta, losses = _pca_step(sample, w)
+    else:
+        theta = np.array(theta_init, np.float64)
+        losses = np.sum(sample ** 2, axis=1) - (sample @ theta) ** 2
     for _ in range(maxiter):
         w = update_weights(losses)
         prev = theta.copy()
@@ -325,8 +398,14 @@ def _cov_step(sample, w):
     return cov, 0.5 * (r + logdet + mu.shape[0] * np.log(2 * np.pi))
 
 
-def covariance(sample, eps, maxiter=100, tol=1e-2):
-    """rlvi.py:128-144."""
+def covariance(sample, eps, maxiter=100, tol=1e-2, *, one_launch=False, return_info=False):
+    """rlvi.py:128-144.  one_launch=True: the whole estimator in ONE launch (limits and return_info as for mean;
+    info[2]: E-steps in which the constraint was active).  Its constrained E-step takes the exact root of the KKT
+    condition where this loop hands its square to scipy's Brent search: the two agree to about 1e-8 relative, not to
+    the bit."""
+    _host_loop_only(one_launch, return_info)
+    if one_launch:
+        return _moments_one_launch("covariance", sample, maxiter, tol, return_info, eps=eps)
     sample = np.asarray(sample, np.float64)
     n = sample.shape[0]
     n_eff = n * (1 - eps)
