@@ -53,7 +53,7 @@ constexpr double LG_NOISE = 1e-12;
 #define LG_STAMP(code) do { } while (0)
 #endif
 
-struct LgShared {
+struct LgShared : SlSolve {      // th: v = (coef, bias), rhs: Z^T (C what s p)
 #if RLVI_STAMPS
     mutable unsigned long long *dbg;
     mutable int nst;
@@ -61,30 +61,13 @@ struct LgShared {
     double *zsh;        // [npad]  z = X coef + bias
     double *hsh;        // [npad]  C what p (1 - p): the Hessian's coefficient
     double *csh;        // [npad]  C what s p: the gradient's coefficient; behind the Gram pass: Z.delta
-    double *red;        // [SL_NW][3][256]  Gram partials of the waves
-    double *G;          // [SL_DP][SL_GPITCH]
-    double *LT;         // [SL_DP][SL_GPITCH]
-    double *th;         // [SL_DP] v = (coef, bias), [SL_DP] the previous fit's
-    double *rhs;        // [SL_DP] Z^T (C what s p)
     double *gv;         // [SL_DP] the gradient
     double *dl;         // [SL_DP] the Newton direction
-    double *slots;      // [2][SL_NW][2]
-    int *flag;          // [4]
 };
 
-// the largest of the threads' values, on every thread (one barrier; the slot discipline of sl_block_sum2)
-__device__ __forceinline__ double lg_block_max(double v, double *slots, int &parity) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    v = wave_max(v);
-    double *s = slots + (size_t)parity * SL_NW * 2;
-    if (lane == 0) s[2 * wave] = v;
-    __syncthreads();
-    double m = s[0];
-#pragma unroll
-    for (int q = 1; q < SL_NW; ++q) m = s[2 * q] > m ? s[2 * q] : m;
-    parity ^= 1;
-    return m;
-}
+// logreg_rlvi_kernel's LDS in doubles: zsh, hsh, csh, gv, dl, then the solve's block
+__host__ __device__ constexpr size_t lg_solve_off(int npad) { return 3 * (size_t)npad + 2 * SL_DP; }
+__host__ __device__ constexpr size_t lg_lds_doubles(int npad) { return lg_solve_off(npad) + SL_SOLVE_DOUBLES; }
 
 // log(1 + exp(-m)), overflow-safe; em = exp(-|m|)
 __device__ __forceinline__ double lg_softplus_neg(double m, double em) {
@@ -98,7 +81,7 @@ __device__ __forceinline__ double lg_softplus_neg(double m, double em) {
 template <int NB>
 __device__ __forceinline__ void lg_gram(const LgShared &sh, const double *__restrict__ X, int n, int d) {
     constexpr int DP = NB * 16;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int i = lane & 15, kk = lane >> 4;
     const int D = d + 1;
     sd4_t a00 = {0.0, 0.0, 0.0, 0.0}, a01 = a00, a11 = a00;
@@ -152,33 +135,8 @@ __device__ __forceinline__ void lg_gram(const LgShared &sh, const double *__rest
             }
         }
     }
-    // the waves' partial blocks -> LDS; element e of a block = (result r, lane): row (lane >> 4) + 4 r, column lane & 15
-    constexpr int NBLK = NB > 1 ? 3 : 1;
-    double *my = sh.red + (size_t)wave * 3 * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        my[0 * 256 + r * 64 + lane] = a00[r];
-        if (DP > 16) {
-            my[1 * 256 + r * 64 + lane] = a01[r];
-            my[2 * 256 + r * 64 + lane] = a11[r];
-        }
-    }
-    __syncthreads();
-    // block sums in wave order (deterministic) -> I + the Gram matrix, padded with the identity to SL_DP rows; the
-    // gradient's part Z^T c (column D) set aside
-    for (int e = tid; e < NBLK * 256; e += SL_THREADS) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < SL_NW; ++w) s += sh.red[(size_t)w * 3 * 256 + e];
-        const int blk = e >> 8, r = (e >> 6) & 3, l = e & 63;
-        const int row = (blk == 2 ? 16 : 0) + (l >> 4) + 4 * r, col = (blk >= 1 ? 16 : 0) + (l & 15);
-        const double one = row == col ? 1.0 : 0.0;
-        const double v = (row < D && col < D) ? s + one : one;
-        sh.G[row * SL_GPITCH + col] = v;
-        if (blk == 1) sh.G[col * SL_GPITCH + row] = v;
-        if (col == D && row < D) sh.rhs[row] = s;
-    }
-    __syncthreads();
+    // the waves' partial blocks -> I + the Gram matrix, the gradient's part Z^T c (column D) set aside
+    sl_gram_collect<NB, true>(sh, D, a00, a01, a11);
 }
 
 // out[r] = x_r . vec[0 .. d) + vec[d] for the rows r < n: 16 rows per wave and instruction on the matrix cores (the
@@ -354,16 +312,10 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
     sh.zsh = sm;
     sh.hsh = sh.zsh + npad;
     sh.csh = sh.hsh + npad;
-    sh.red = sh.csh + npad;
-    sh.G = sh.red + SL_NW * 3 * 256;
-    sh.LT = sh.G + SL_DP * SL_GPITCH;
-    sh.th = sh.LT + SL_DP * SL_GPITCH;
-    sh.rhs = sh.th + 2 * SL_DP;
-    sh.gv = sh.rhs + SL_DP;
+    sh.gv = sh.csh + npad;
     sh.dl = sh.gv + SL_DP;
-    sh.slots = sh.dl + SL_DP;
-    sh.flag = reinterpret_cast<int *>(sh.slots + 2 * SL_NW * 2);
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    sl_solve_carve(sh, sm + lg_solve_off(npad));
+    const int tid = threadIdx.x;
     const int D = d + 1;
     int parity = 0;
 
@@ -384,7 +336,7 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
     for (int q = tid; q < 2 * SL_DP; q += SL_THREADS) sh.th[q] = 0.0;
     for (int q = tid; q < SL_DP * SL_GPITCH; q += SL_THREADS) sh.G[q] = 0.0;
     sl_block_sum2(nbad, none, sh.slots, parity);
-    wmax = lg_block_max(wmax, sh.slots, parity);
+    wmax = sl_block_max(wmax, sh.slots, parity);
     bool ok = nbad == 0.0 && wmax > 0.0;
 #pragma unroll
     for (int j = 0; j < E; ++j) cw[j] = creg * (w[j] / wmax);                    // utils.py:66: weights / max
@@ -397,12 +349,7 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
         if (rc == 1) { ok = false; break; }
         capped = capped || rc == 2;
         if (mode != 0) break;
-        if (outer > 0) {
-            // ||theta - prev|| / ||prev|| <= tol (rlvi.py:104-106): every wave from LDS, the same bits everywhere
-            const double tn = lane < D ? sh.th[lane] : 0.0, tp = lane < D ? sh.th[SL_DP + lane] : 0.0;
-            const double dn = wave_sum((tn - tp) * (tn - tp)), pn = wave_sum(tp * tp);
-            if (sqrt(dn) / sqrt(pn) <= tol) break;
-        }
+        if (outer > 0 && !sl_theta_moved(sh.th, D, tol)) break;      // rlvi.py:104-106
         if (outer >= maxiter) break;
         ++outer;
         // ---- update_weights(losses) (rlvi.py:98 -> :8-20); losses = -log p(class 0 | x) = log(1 + exp(z)) for every
@@ -422,7 +369,7 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
         wmax = 0.0;
 #pragma unroll
         for (int j = 0; j < E; ++j) wmax = w[j] > wmax ? w[j] : wmax;
-        wmax = lg_block_max(wmax, sh.slots, parity);
+        wmax = sl_block_max(wmax, sh.slots, parity);
         if (!(wmax > 0.0)) { ok = false; break; }
 #pragma unroll
         for (int j = 0; j < E; ++j) cw[j] = creg * (w[j] / wmax);
@@ -460,8 +407,7 @@ static int lg_launch(const double *X, const double *y, const double *w_in, int64
                      int maxiter, double tol, double etol, int emaxiter, double creg, double *theta, double *w_out,
                      double *losses, int32_t *info, void *ws, hipStream_t st) {
     const int npad = (int)((n + 63) / 64) * 64;
-    const size_t lds = ((size_t)3 * npad + (size_t)SL_NW * 3 * 256 + 2 * SL_DP * SL_GPITCH + 5 * SL_DP +
-                        2 * SL_NW * 2 + 2) * sizeof(double);
+    const size_t lds = lg_lds_doubles(npad) * sizeof(double);
     int32_t *status = &static_cast<WsHeader *>(ws)->status;
     auto go = [&](auto kern) {
         // (asked for per kernel: allow_dyn_lds keeps its once-per-device state by the kernel's address)
@@ -493,24 +439,20 @@ extern "C" int rlvi_logistic_regression_check(int64_t n, int64_t d) { return lg_
 extern "C" int rlvi_logistic_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
                                             double tol, double estep_tol, int estep_maxiter, double C, double *theta,
                                             double *weights, double *losses, int32_t *info, void *ws, void *stream) {
-    if (!X || !y || !theta || !weights || !info || !ws) return RLVI_E_NULL;
+    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
     if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0 || !(C > 0.0)) return RLVI_E_SHAPE;
     if (lg_check(n, d)) return RLVI_E_LIMIT;
-    if (((uintptr_t)X & 7) || ((uintptr_t)y & 7) || ((uintptr_t)theta & 7) || ((uintptr_t)weights & 7) ||
-        ((uintptr_t)losses & 7) || ((uintptr_t)info & 3) || ((uintptr_t)ws & 255))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({X, y, theta, weights, losses}, info, ws)) return RLVI_E_ALIGN;
     return lg_launch(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses, info,
                      ws, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int rlvi_logistic_fit_f64(const double *X, const double *y, const double *w, int64_t n, int64_t d, double C,
                                      double *theta, double *losses, int32_t *info, void *ws, void *stream) {
-    if (!X || !y || !w || !theta || !losses || !info || !ws) return RLVI_E_NULL;
+    if (sl_any_null({X, y, w, theta, losses, info, ws})) return RLVI_E_NULL;
     if (n <= 0 || d <= 0 || !(C > 0.0)) return RLVI_E_SHAPE;
     if (lg_check(n, d)) return RLVI_E_LIMIT;
-    if (((uintptr_t)X & 7) || ((uintptr_t)y & 7) || ((uintptr_t)w & 7) || ((uintptr_t)theta & 7) ||
-        ((uintptr_t)losses & 7) || ((uintptr_t)info & 3) || ((uintptr_t)ws & 255))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({X, y, w, theta, losses}, info, ws)) return RLVI_E_ALIGN;
     return lg_launch(X, y, w, n, d, 1, 0, 0.0, 0.0, 0, C, theta, nullptr, losses, info, ws,
                      static_cast<hipStream_t>(stream));
 }

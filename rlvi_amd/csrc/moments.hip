@@ -14,7 +14,7 @@
 //     tid + 256 j and keeps their weights and losses in registers;
 //   * weighted moments are TWO passes -- sum a and sum a x, then sum a (x - m)(x - m)^T about the mean just found (never
 //     S2 - m m^T: a cloud at 1e6 with unit spread would lose twelve digits) --, each ONE block sum of K values behind
-//     one barrier (mo_block_sum: sl_block_sum2 for K values);
+//     one barrier (sl_block_sum<K>);
 //   * the d x d algebra (d <= 8, padded to 2 / 4 / 8) runs on EVERY thread, redundantly, in registers, from the same
 //     LDS totals: an L D L^T factorisation with the pivot test of sl_ldlt_solve (covariance), cyclic Jacobi sweeps
 //     (PCA) -- no broadcast, no further barrier;
@@ -35,56 +35,14 @@ constexpr int MO_MAXND = 16384;                    // n d doubles of the sample 
 constexpr int MO_KMAX = 36;                        // values of one block sum: the lower triangle of 8 x 8
 constexpr int MO_JACOBI_CAP = 30;                  // sweeps of one eigen-solve
 constexpr int MO_ROOT_CAP = 200;                   // evaluations of one root-find
-constexpr double MO_EPS = 2.220446049250313e-16;
+constexpr double MO_EPS = SL_EPS;
 
 struct MoShared {
     const double *xs;   // [n * d] the sample
-    double *kslots;     // [2][SL_NW][MO_KMAX]  mo_block_sum / mo_block_minmax
-    double *slots;      // [2][SL_NW][2]        sl_block_sum2 (an area of its own: the two layouts must not overlap)
+    double *slots;      // [2][SL_NW][MO_KMAX]  every block reduction of these kernels, the E-step's included
 };
 
 __host__ __device__ constexpr int mo_tri(int i, int j) { return i * (i + 1) / 2 + j; }     // j <= i
-
-// v[0 .. K) summed over the workgroup, every thread gets the totals: sl_block_sum2 for K values, ONE barrier, the
-// waves' partial sums added in wave order
-template <int K>
-__device__ __forceinline__ void mo_block_sum(double (&v)[K], double *kslots, int &parity) {
-    static_assert(K <= MO_KMAX, "slot size");
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    double *s = kslots + (size_t)parity * SL_NW * MO_KMAX;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = wave_sum(v[k]);
-        if (lane == 0) s[wave * MO_KMAX + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < SL_NW; ++w) t += s[w * MO_KMAX + k];
-        v[k] = t;
-    }
-    parity ^= 1;
-}
-
-// the smallest and the largest of the threads' values, on every thread (one barrier, the same slots)
-__device__ __forceinline__ void mo_block_minmax(double &lo, double &hi, double *kslots, int &parity) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    double *s = kslots + (size_t)parity * SL_NW * MO_KMAX;
-    lo = wave_min(lo);
-    hi = wave_max(hi);
-    if (lane == 0) { s[wave * MO_KMAX] = lo; s[wave * MO_KMAX + 1] = hi; }
-    __syncthreads();
-    double a = s[0], b = s[1];
-#pragma unroll
-    for (int w = 1; w < SL_NW; ++w) {
-        a = s[w * MO_KMAX] < a ? s[w * MO_KMAX] : a;
-        b = s[w * MO_KMAX + 1] > b ? s[w * MO_KMAX + 1] : b;
-    }
-    lo = a; hi = b;
-    parity ^= 1;
-}
 
 // row q of the sample, 0 beyond its d columns and for a sample past n
 template <int DS>
@@ -218,7 +176,7 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
 #pragma unroll
             for (int c = 0; c < DS; ++c) s1[1 + c] = __builtin_fma(w[j], x[c], s1[1 + c]);
         }
-        mo_block_sum<1 + DS>(s1, sh.kslots, parity);
+        sl_block_sum<1 + DS, MO_KMAX>(s1, sh.slots, parity);
         const double s0 = s1[0];
         if (!(s0 > 0.0 && s0 < __builtin_inf())) return 1;
         double m[DS];
@@ -238,7 +196,7 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
                 l[j] = q < n ? r : 0.0;
                 swr = __builtin_fma(w[j], l[j], swr);
             }
-            sl_block_sum2(swr, none, sh.slots, parity);
+            sl_block_sum2<MO_KMAX>(swr, none, sh.slots, parity);
             const double sigma2 = swr / s0;
             if (!(sigma2 > 0.0 && sigma2 < __builtin_inf())) return 1;
 #pragma unroll
@@ -269,7 +227,7 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
                 for (int c2 = 0; c2 <= c1; ++c2) a2[mo_tri(c1, c2)] = __builtin_fma(yc, y[c2], a2[mo_tri(c1, c2)]);
             }
         }
-        mo_block_sum<NTRI>(a2, sh.kslots, parity);
+        sl_block_sum<NTRI, MO_KMAX>(a2, sh.slots, parity);
         if (MODE == 1) {
             double t[DS];
             rc = mo_jacobi_top<DS>(a2, d, t, sweeps);
@@ -291,7 +249,7 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
                 }
                 if (i < d) dmax = g[mo_tri(i, i)] > dmax ? g[mo_tri(i, i)] : dmax;
             }
-            const double piv_min = dmax * (double)d * 64.0 * MO_EPS;
+            const double piv_min = sl_pivot_floor(dmax, d);
             bool bad = !(dmax < __builtin_inf());
             double logdet = 0.0;
 #pragma unroll
@@ -370,11 +328,11 @@ __device__ __forceinline__ int mo_estep_constrained(const double (&l)[E], double
         e[j] = v ? exp(-l[j]) : 0.0;
         w[j] = v ? 0.95 : 0.0;                                      // rlvi.py:10
     }
-    inner = sl_estep_fixed_point<E>(e, w, n, etol, emaxiter, sh.slots, parity);
+    inner = sl_estep_fixed_point<E, MO_KMAX>(e, w, n, etol, emaxiter, sh.slots, parity);
     double sum = 0.0, none = 0.0;
 #pragma unroll
     for (int j = 0; j < E; ++j) sum += w[j];
-    sl_block_sum2(sum, none, sh.slots, parity);
+    sl_block_sum2<MO_KMAX>(sum, none, sh.slots, parity);
     active = sum < n_eff;                                           // rlvi.py:40
     evals = 0;
     if (!active) return 0;
@@ -385,7 +343,7 @@ __device__ __forceinline__ int mo_estep_constrained(const double (&l)[E], double
         lo = (v && l[j] < lo) ? l[j] : lo;
         hi = (v && l[j] > hi) ? l[j] : hi;
     }
-    mo_block_minmax(lo, hi, sh.kslots, parity);
+    sl_block_minmax<MO_KMAX>(lo, hi, sh.slots, parity);
     const double c = ((double)n - n_eff) / n_eff;
     // where the fixed point stopped: its weights are 1 / (1 + ratio exp(l)), i.e. the shift log(c / ratio)
     double s;
@@ -404,7 +362,7 @@ __device__ __forceinline__ int mo_estep_constrained(const double (&l)[E], double
             g += t;
             gp = __builtin_fma(t, 1.0 - t, gp);
         }
-        sl_block_sum2(g, gp, sh.slots, parity);
+        sl_block_sum2<MO_KMAX>(g, gp, sh.slots, parity);
         ++evals;
         const double f = g - n_eff;
         if (fabs(f) <= gtol) break;
@@ -431,14 +389,13 @@ __device__ __forceinline__ int mo_estep_constrained(const double (&l)[E], double
     return rc;
 }
 
+// the kernels' LDS in doubles: the sample (an even count), then the slots
+__host__ __device__ constexpr size_t mo_slots_off(int64_t nd) { return (size_t)((nd + 1) & ~(int64_t)1); }
 __device__ __forceinline__ void mo_carve(MoShared &sh, double *sm, int nd) {
     sh.xs = sm;
-    sh.kslots = sm + ((nd + 1) & ~1);
-    sh.slots = sh.kslots + 2 * SL_NW * MO_KMAX;
+    sh.slots = sm + mo_slots_off(nd);
 }
-static size_t mo_lds_bytes(int64_t nd) {
-    return ((size_t)((nd + 1) & ~(int64_t)1) + 2 * SL_NW * MO_KMAX + 2 * SL_NW * 2) * sizeof(double);
-}
+static size_t mo_lds_bytes(int64_t nd) { return (mo_slots_off(nd) + sl_slot_doubles(MO_KMAX)) * sizeof(double); }
 
 // MODE 0 / 1 / 2: mean / pca / covariance.  theta_out: [d], [d], [d * d]; info: { outer iterations, inner iterations of
 // the last E-step, inner iterations in all | Jacobi sweeps in all | E-steps with the constraint active, flag }.
@@ -475,7 +432,7 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
         }
     }
     if (MODE == 2 && !(n_eff > 0.0 && n_eff < (double)n)) nbad += 1.0;
-    sl_block_sum2(nbad, none, sh.slots, parity);                    // (its barrier publishes the sample)
+    sl_block_sum2<MO_KMAX>(nbad, none, sh.slots, parity);                    // (its barrier publishes the sample)
     bool ok = nbad == 0.0;
 
     double w[E], l[E];
@@ -508,7 +465,7 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
                 e[j] = v ? exp(-l[j]) : 0.0;
                 w[j] = v ? 0.95 : 0.0;                              // rlvi.py:10
             }
-            inner_last = sl_estep_fixed_point<E>(e, w, n, etol, emaxiter, sh.slots, parity);
+            inner_last = sl_estep_fixed_point<E, MO_KMAX>(e, w, n, etol, emaxiter, sh.slots, parity);
             if (MODE == 0) count += inner_last;
         }
 #pragma unroll
@@ -595,7 +552,7 @@ __global__ __launch_bounds__(SL_THREADS) void moments_uwc_kernel(const double *_
         if (q < n && !(fabs(l[j]) < __builtin_inf())) nbad += 1.0;
     }
     if (!(n_eff > 0.0 && n_eff < (double)n)) nbad += 1.0;
-    sl_block_sum2(nbad, none, sh.slots, parity);
+    sl_block_sum2<MO_KMAX>(nbad, none, sh.slots, parity);
     const bool ok = nbad == 0.0;
     int inner = 0, evals = 0, rc = 0;
     bool active = false;
@@ -648,13 +605,10 @@ static int mo_launch(const double *X, const double *theta_init, int64_t n, int64
 
 static int mo_args(const double *sample, int64_t n, int64_t d, int maxiter, int estep_maxiter, const double *theta_init,
                    double *theta, double *weights, int32_t *info, void *ws) {
-    if (!sample || !theta || !weights || !info || !ws) return RLVI_E_NULL;
+    if (sl_any_null({sample, theta, weights, info, ws})) return RLVI_E_NULL;
     if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
     if (mo_check(n, d)) return RLVI_E_LIMIT;
-    if (((uintptr_t)sample & 7) || ((uintptr_t)theta_init & 7) || ((uintptr_t)theta & 7) || ((uintptr_t)weights & 7) ||
-        ((uintptr_t)info & 3) || ((uintptr_t)ws & 255))
-        return RLVI_E_ALIGN;
-    return 0;
+    return sl_misaligned({sample, theta_init, theta, weights}, info, ws) ? RLVI_E_ALIGN : 0;
 }
 
 }  // namespace rlvi
@@ -689,11 +643,10 @@ extern "C" int rlvi_robust_covariance_f64(const double *sample, int64_t n, int64
 
 extern "C" int rlvi_update_weights_constrained_f64(const double *losses, int64_t n, double n_eff, double tol,
                                                    int maxiter, double *out, int32_t *info, void *ws, void *stream) {
-    if (!losses || !out || !info || !ws) return RLVI_E_NULL;
+    if (sl_any_null({losses, out, info, ws})) return RLVI_E_NULL;
     if (n <= 0 || maxiter < 0) return RLVI_E_SHAPE;
     if (n > SL_MAXN) return RLVI_E_LIMIT;
-    if (((uintptr_t)losses & 7) || ((uintptr_t)out & 7) || ((uintptr_t)info & 3) || ((uintptr_t)ws & 255))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({losses, out}, info, ws)) return RLVI_E_ALIGN;
     int32_t *status = &static_cast<WsHeader *>(ws)->status;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t lds = mo_lds_bytes(0);

@@ -58,6 +58,11 @@ struct SlShared {
     double *x1s;        // [1024][8]  columns 16 .. 23 of [X | y] (resident design with two column blocks)
 };
 
+// linreg_rlvi_kernel's LDS in doubles: wsh, rsh, the solve's block, x1s where the resident design has a second block
+__host__ __device__ constexpr size_t sl_lds_doubles(int npad, bool x1s) {
+    return 2 * (size_t)npad + SL_SOLVE_DOUBLES + (x1s ? 1024 * 8 : 0);
+}
+
 // theta = argmin sum_i w_i (y_i - x_i.theta)^2 from the weights in sh.wsh -> sh.th[0 .. d).  Returns false (on
 // every thread) when a pivot is not safely positive.  All threads call.  DS: the system is solved padded to DS >= d
 // rows -- straight-line code, no guard inside the factorisation; NB: 16-column blocks of [X | y] (2 when d >= 16).
@@ -182,8 +187,8 @@ __device__ __forceinline__ bool sl_wls(const SlShared &sh, const double *__restr
     __syncthreads();
     SL_STAMP();   // block sums done
     // ---- wave 0: G = L D L^T, row t of the lower triangle in lane t's registers
-    // (the same code as sl_ldlt_solve of rlvi_sl.h, which logreg.hip calls: kept in place here because calling it moves
-    //  this kernel's register allocation -- a change to either copy belongs in both)
+    // (sl_ldlt_solve<DS> of rlvi_sl.h in place: the call moves this kernel's register allocation, and with it single
+    //  cells of tools/lab/sweep_linreg.py by up to 2 % either way -- profiles/r17_sl_header.md)
     if (wave == 0) {
         int t = lane & (SL_DP - 1);
         // (opaque: the lane masks t > j, t == j below are loop-invariant across the estimator's outer loop, and
@@ -195,7 +200,7 @@ __device__ __forceinline__ bool sl_wls(const SlShared &sh, const double *__restr
         double b = t < d ? sh.rhs[t < SL_DP ? t : 0] : 0.0;
         double dmax = t < d ? sh.G[t * SL_GPITCH + t] : 0.0;
         dmax = wave_max(dmax);
-        const double piv_min = dmax * (double)d * 64.0 * 2.220446049250313e-16;
+        const double piv_min = sl_pivot_floor(dmax, d);
         bool bad = !(dmax == dmax);
         double dinv = 0.0;                       // lane j: 1 / D_j
 #pragma unroll
@@ -369,14 +374,17 @@ __global__ __launch_bounds__(SL_THREADS) void linreg_rlvi_kernel(
 #endif
     sh.wsh = sm;
     sh.rsh = sh.wsh + npad;
-    sh.red = sh.rsh + npad;
-    sh.G = sh.red + SL_NW * 3 * 256;
-    sh.LT = sh.G + SL_DP * SL_GPITCH;
-    sh.th = sh.LT + SL_DP * SL_GPITCH;
-    sh.rhs = sh.th + 2 * SL_DP;
-    sh.slots = sh.rhs + SL_DP;
-    sh.flag = reinterpret_cast<int *>(sh.slots + 2 * SL_NW * 2);
-    sh.x1s = reinterpret_cast<double *>(sh.flag + 4);
+    // (the solve's block from rlvi_sl.h's offset table, spelled out: sl_solve_carve on a base struct moves this
+    //  kernel's register allocation)
+    double *const solve = sh.rsh + npad;
+    sh.red = solve + SL_OFF_RED;
+    sh.G = solve + SL_OFF_G;
+    sh.LT = solve + SL_OFF_LT;
+    sh.th = solve + SL_OFF_TH;
+    sh.rhs = solve + SL_OFF_RHS;
+    sh.slots = solve + SL_OFF_SLOTS;
+    sh.flag = reinterpret_cast<int *>(solve + SL_OFF_FLAG);
+    sh.x1s = solve + SL_SOLVE_DOUBLES;                  // (= sm + sl_lds_doubles(npad, false))
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     int parity = 0;
 
@@ -453,8 +461,7 @@ __global__ __launch_bounds__(SL_THREADS) void linreg_rlvi_kernel(
             e[j] = v ? exp(-(sh.rsh[v ? q : 0] * hs)) : 0.0;      // losses = 0.5 r / sigma2 (rlvi.py:74); exp(-losses)
             w[j] = v ? 0.95 : 0.0;                                 // rlvi.py:10
         }
-        // (the same loop as sl_estep_fixed_point of rlvi_sl.h: in place here for the same reason as the factorisation
-        //  in sl_wls -- a change to either copy belongs in both)
+        // (sl_estep_fixed_point<E> of rlvi_sl.h in place, for the same reason as the factorisation in sl_wls)
         double ratio;
         { const double eps = 1.0 - 0.95; ratio = eps / (1.0 - eps); }
         int it = 0;
@@ -512,7 +519,7 @@ __global__ __launch_bounds__(SL_THREADS) void online_weight_kernel(
     const double *__restrict__ X, const double *__restrict__ wv, double b, int first, int n, int d, double tol,
     int maxiter, double *__restrict__ losses_out, double *__restrict__ out, int32_t *__restrict__ out_iters) {
     __shared__ double lsh[SL_MAXN];
-    __shared__ double slots[2 * SL_NW * 2];
+    __shared__ double slots[sl_slot_doubles(2)];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const int i = lane & 15, kk = lane >> 4;
     int parity = 0;
@@ -606,13 +613,7 @@ __global__ __launch_bounds__(SL_THREADS) void online_weight_kernel(
 #pragma unroll
     for (int j = 0; j < E; ++j)
         if (tid + j * SL_THREADS < n) mx = w[j] > mx ? w[j] : mx;
-    mx = wave_max(mx);
-    double *s = slots + (size_t)parity * SL_NW * 2;
-    if (lane == 0) s[2 * wave] = mx;
-    __syncthreads();
-    mx = s[0];
-#pragma unroll
-    for (int q = 1; q < SL_NW; ++q) mx = s[2 * q] > mx ? s[2 * q] : mx;
+    mx = sl_block_max(mx, slots, parity);
     const double den = mx * (double)n;
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -636,12 +637,10 @@ extern "C" int rlvi_linear_regression_check(int64_t n, int64_t d) {
 extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
                                           double tol, double estep_tol, int estep_maxiter, double *theta,
                                           double *weights, int32_t *info, void *ws, void *stream) {
-    if (!X || !y || !theta || !weights || !info || !ws) return RLVI_E_NULL;
+    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
     if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
     if (n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
-    if (((uintptr_t)X & 7) || ((uintptr_t)y & 7) || ((uintptr_t)theta & 7) || ((uintptr_t)weights & 7) ||
-        ((uintptr_t)info & 3) || ((uintptr_t)ws & 255))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // (samples per thread: four up to n = 1024, sixteen beyond; the system solved padded to 12 / 16 / 20 / 24 / 32 rows;
     //  one or two 16-column blocks of [X | y]; the design resident on the chip -- registers + LDS -- when n <= 1024
@@ -649,8 +648,7 @@ extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int6
     const bool two = d >= 16;                                     // column d (= y) needs the second block
     const bool res = n <= 4 * SL_THREADS && d <= 23;
     const int npad_x = res ? 1024 : (int)((n + 63) / 64) * 64;
-    const size_t lds = ((size_t)2 * npad_x + (size_t)SL_NW * 3 * 256 + 2 * SL_DP * SL_GPITCH + 3 * SL_DP +
-                        2 * SL_NW * 2 + 2 + ((res && two) ? 1024 * 8 : 0)) * sizeof(double);
+    const size_t lds = sl_lds_doubles(npad_x, res && two) * sizeof(double);
     auto go = [&](auto kern) {
         if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
         return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d, npad_x, maxiter, tol,
@@ -674,11 +672,10 @@ extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int6
 extern "C" int rlvi_sample_weight_online_f64(const double *X, const double *w, double b, int first, int64_t n,
                                              int64_t d, double tol, int maxiter, double *losses_out,
                                              double *sample_weight, int32_t *out_iters, void *stream) {
-    if (!sample_weight || (!first && (!X || !w))) return RLVI_E_NULL;
+    if (!sample_weight || (!first && sl_any_null({X, w}))) return RLVI_E_NULL;
     if (n <= 0 || d <= 0 || maxiter < 0) return RLVI_E_SHAPE;
     if (n > SL_MAXN) return RLVI_E_LIMIT;
-    if (((uintptr_t)X & 7) || ((uintptr_t)w & 7) || ((uintptr_t)sample_weight & 7) || ((uintptr_t)losses_out & 7))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({X, w, sample_weight, losses_out})) return RLVI_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define RLVI_OW(E_)                                                                                         \
     return launch(online_weight_kernel<E_>, dim3(1), dim3(SL_THREADS), 0, st, X, w, b, first, (int)n, (int)d, \

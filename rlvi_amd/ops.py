@@ -535,28 +535,42 @@ def linear_regression_check(n, d):
     return _lib.load().rlvi_linear_regression_check(int(n), int(d)) == 0
 
 
+def _fp64(t, dims=None, numel=None):
+    """t is a contiguous fp64 tensor (of `dims` dimensions, of `numel` elements, where given)"""
+    return (t.dtype == torch.float64 and t.is_contiguous() and (dims is None or t.dim() == dims)
+            and (numel is None or t.numel() == numel))
+
+
+def _one_launch(entry, inputs, args, outs, info, ws):
+    """The call of a one-launch fp64 estimator on inputs its wrapper has checked:
+    entry(*inputs, *inputs[0].shape, *args, *outs, info, ws, stream).  outs: one (tensor, elements) per output array;
+    a tensor that is None is allocated here with that many elements -- or, with elements None as well, passed as
+    NULL (an optional output).  info and the workspace are made when not given.  Returns (*outs, info)."""
+    L = _lib.load()
+    X = inputs[0]
+    outs = [torch.empty(numel, dtype=torch.float64, device=X.device) if t is None and numel is not None else t
+            for t, numel in outs]
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int32, device=X.device)
+    ws = ws or workspace(X.device, X.shape[0], 0)
+    _lib.check(getattr(L, entry)(*(_ptr(t) for t in inputs), *X.shape, *args, *(_ptr(t) for t in outs), _ptr(info),
+                                 ws.ptr, _stream_ptr()), entry)
+    return (*outs, info)
+
+
 def linear_regression(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None,
                       info=None, ws=None):
     """linear_regression(X, y, maxiter, tol) of standard-learning/rlvi.py:68-89 as ONE launch on device tensors
     (no host synchronisation here).  Returns (theta [d], weights [n], info int32[4] = {outer iterations, inner
     iterations of the last E-step, inner iterations in all, fallback}) -- info[3] == 1 (rank-deficient design):
     theta / weights were not written, compose wls_solve / linreg_losses / update_weights_f64 instead."""
-    L = _lib.load()
     _require_gpu(X, y)
-    if X.dtype != torch.float64 or y.dtype != torch.float64 or not X.is_contiguous() or not y.is_contiguous():
+    if not (_fp64(X) and _fp64(y)):
         raise ValueError("X [n, d] and y [n] must be contiguous fp64 device tensors")
     n, d = X.shape
-    if theta is None:
-        theta = torch.empty(d, dtype=torch.float64, device=X.device)
-    if weights is None:
-        weights = torch.empty(n, dtype=torch.float64, device=X.device)
-    if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=X.device)
-    ws = ws or workspace(X.device, n, 0)
-    _lib.check(L.rlvi_linear_regression_f64(_ptr(X), _ptr(y), n, d, int(maxiter), float(tol), float(estep_tol),
-                                            int(estep_maxiter), _ptr(theta), _ptr(weights), _ptr(info), ws.ptr,
-                                            _stream_ptr()), "rlvi_linear_regression_f64")
-    return theta, weights, info
+    return _one_launch("rlvi_linear_regression_f64", (X, y),
+                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+                       ((theta, d), (weights, n)), info, ws)
 
 
 def logistic_regression_check(n, d):
@@ -566,11 +580,10 @@ def logistic_regression_check(n, d):
 
 def _logistic_inputs(X, *vectors):
     _require_gpu(X, *vectors)
-    if X.dim() != 2 or X.dtype != torch.float64 or not X.is_contiguous():
+    if not _fp64(X, dims=2):
         raise ValueError("X [n, d] must be a contiguous fp64 device tensor")
-    for v in vectors:
-        if v.dtype != torch.float64 or not v.is_contiguous() or v.numel() != X.shape[0]:
-            raise ValueError("y and the weights must be contiguous fp64 device tensors of X's n elements")
+    if not all(_fp64(v, numel=X.shape[0]) for v in vectors):
+        raise ValueError("y and the weights must be contiguous fp64 device tensors of X's n elements")
     return X.shape
 
 
@@ -581,18 +594,8 @@ def logistic_fit(X, y, w, C=100.0, theta=None, losses=None, info=None, ws=None):
     (intercept, coef), losses [n] = log(1 + exp(z)), info int32[4] = {0, 0, Newton steps, flag}); flag 1: nothing
     was written (data not finite, y not 0 / 1, no positive weight, a pivot not safely positive); flag 2: the Newton cap, or a line search
     without an acceptable step (RLVI_ST_NOCONV in ws)."""
-    L = _lib.load()
     n, d = _logistic_inputs(X, y, w)
-    if theta is None:
-        theta = torch.empty(d + 1, dtype=torch.float64, device=X.device)
-    if losses is None:
-        losses = torch.empty(n, dtype=torch.float64, device=X.device)
-    if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=X.device)
-    ws = ws or workspace(X.device, n, 0)
-    _lib.check(L.rlvi_logistic_fit_f64(_ptr(X), _ptr(y), _ptr(w), n, d, float(C), _ptr(theta), _ptr(losses),
-                                       _ptr(info), ws.ptr, _stream_ptr()), "rlvi_logistic_fit_f64")
-    return theta, losses, info
+    return _one_launch("rlvi_logistic_fit_f64", (X, y, w), (float(C),), ((theta, d + 1), (losses, n)), info, ws)
 
 
 def logistic_regression(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, C=100.0, theta=None,
@@ -601,18 +604,11 @@ def logistic_regression(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxit
     (rlvi_logistic_regression_f64; no host synchronisation here).  Returns (theta [d + 1] = (intercept, coef),
     weights [n], info int32[4] = {outer iterations, inner iterations of the last E-step, Newton steps in all, flag});
     `losses` [n], if given, receives the last fit's.  flag as logistic_fit."""
-    L = _lib.load()
     n, d = _logistic_inputs(X, y)
-    if theta is None:
-        theta = torch.empty(d + 1, dtype=torch.float64, device=X.device)
-    if weights is None:
-        weights = torch.empty(n, dtype=torch.float64, device=X.device)
-    if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=X.device)
-    ws = ws or workspace(X.device, n, 0)
-    _lib.check(L.rlvi_logistic_regression_f64(_ptr(X), _ptr(y), n, d, int(maxiter), float(tol), float(estep_tol),
-                                              int(estep_maxiter), float(C), _ptr(theta), _ptr(weights), _ptr(losses),
-                                              _ptr(info), ws.ptr, _stream_ptr()), "rlvi_logistic_regression_f64")
+    theta, weights, _, info = _one_launch(
+        "rlvi_logistic_regression_f64", (X, y),
+        (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter), float(C)),
+        ((theta, d + 1), (weights, n), (losses, None)), info, ws)
     return theta, weights, info
 
 
@@ -622,22 +618,11 @@ def moments_check(n, d):
     return _lib.load().rlvi_moments_check(int(n), int(d)) == 0
 
 
-def _moments_call(entry, sample, theta_numel, theta, weights, info, ws, args):
-    L = _lib.load()
+def _sample_shape(sample):
     _require_gpu(sample)
-    if sample.dim() != 2 or sample.dtype != torch.float64 or not sample.is_contiguous():
+    if not _fp64(sample, dims=2):
         raise ValueError("sample [n, d] must be a contiguous fp64 device tensor")
-    n, d = sample.shape
-    if theta is None:
-        theta = torch.empty(theta_numel(d), dtype=torch.float64, device=sample.device)
-    if weights is None:
-        weights = torch.empty(n, dtype=torch.float64, device=sample.device)
-    if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=sample.device)
-    ws = ws or workspace(sample.device, n, 0)
-    _lib.check(getattr(L, entry)(_ptr(sample), n, d, *args, _ptr(theta), _ptr(weights), _ptr(info), ws.ptr,
-                                 _stream_ptr()), entry)
-    return theta, weights, info
+    return sample.shape
 
 
 def robust_mean(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None, info=None,
@@ -646,8 +631,10 @@ def robust_mean(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100
     (rlvi_robust_mean_f64; no host synchronisation here).  Returns (theta [d], weights [n], info int32[4] = {outer
     iterations, inner iterations of the last E-step, inner iterations in all, flag}); flag 1: nothing was written
     (data not finite, a variance not safely positive)."""
-    return _moments_call("rlvi_robust_mean_f64", sample, lambda d: d, theta, weights, info, ws,
-                         (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)))
+    n, d = _sample_shape(sample)
+    return _one_launch("rlvi_robust_mean_f64", (sample,),
+                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+                       ((theta, d), (weights, n)), info, ws)
 
 
 def robust_pca(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, estep_maxiter=100, theta=None,
@@ -658,10 +645,12 @@ def robust_pca(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, e
     eigen-solve hit its 30 sweeps (RLVI_ST_NOCONV in ws)."""
     if theta_init is not None:
         _require_gpu(theta_init)
-        if theta_init.dtype != torch.float64 or not theta_init.is_contiguous() or theta_init.numel() != sample.shape[1]:
+        if not _fp64(theta_init, numel=sample.shape[1]):
             raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
-    return _moments_call("rlvi_robust_pca_f64", sample, lambda d: d, theta, weights, info, ws,
-                         (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)))
+    n, d = _sample_shape(sample)
+    return _one_launch("rlvi_robust_pca_f64", (sample,),
+                       (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)),
+                       ((theta, d), (weights, n)), info, ws)
 
 
 def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, theta=None,
@@ -670,10 +659,11 @@ def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, este
     launch on device tensors (rlvi_robust_covariance_f64).  Returns (theta [d, d], weights [n], info = {outer, inner
     of the last E-step, E-steps with the constraint active, flag}); flag 1: nothing was written (data not finite, a
     pivot not safely positive, n_eff outside (0, n)); flag 2: a root-find hit its cap (RLVI_ST_NOCONV in ws)."""
-    theta, weights, info = _moments_call("rlvi_robust_covariance_f64", sample,
-                                         lambda d: d * d, None if theta is None else theta.view(-1), weights, info, ws,
-                                         (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)))
-    d = sample.shape[1]
+    n, d = _sample_shape(sample)
+    theta, weights, info = _one_launch(
+        "rlvi_robust_covariance_f64", (sample,),
+        (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+        ((None if theta is None else theta.view(-1), d * d), (weights, n)), info, ws)
     return theta.view(d, d), weights, info
 
 
@@ -683,20 +673,11 @@ def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, i
     weights sum to less than n_eff, the weights 1 / (1 + c exp(l - s)) at the exact root s of their sum = n_eff.
     Returns (weights [n], info int32[4] = {root-find evaluations, the fixed point's iterations, 1 if the constraint
     was active, flag})."""
-    L = _lib.load()
     _require_gpu(losses)
-    if losses.dim() != 1 or losses.dtype != torch.float64 or not losses.is_contiguous():
+    if not _fp64(losses, dims=1):
         raise ValueError("losses [n] must be a contiguous fp64 device tensor")
-    n = losses.shape[0]
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=losses.device)
-    if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=losses.device)
-    ws = ws or workspace(losses.device, n, 0)
-    _lib.check(L.rlvi_update_weights_constrained_f64(_ptr(losses), n, float(n_eff), float(tol), int(maxiter), _ptr(out),
-                                                     _ptr(info), ws.ptr, _stream_ptr()),
-               "rlvi_update_weights_constrained_f64")
-    return out, info
+    return _one_launch("rlvi_update_weights_constrained_f64", (losses,), (float(n_eff), float(tol), int(maxiter)),
+                       ((out, losses.shape[0]),), info, ws)
 
 
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,

@@ -81,6 +81,28 @@ def _roundtrip_f64(host_in, fn):
     return h_out.numpy().copy().reshape(shape)
 
 
+def _one_launch_roundtrip(dev, tag, parts, nt, n, launch):
+    """The numpy-in / numpy-out call of a one-launch estimator: the host arrays `parts` = [(array or None, length)]
+    packed into ONE pinned buffer and copied to the device, launch(device views of the parts, dict(theta [nt],
+    weights [n], info int32[4])), ONE pinned copy of {theta, weights, info} back and the one host wait of the call.
+    Returns (theta, weights, info) as views of the pinned result -- copy what is handed out -- and the device views."""
+    total = sum(length for _, length in parts)
+    h_in, h_out, d_in, d_out = _STAGE.get(dev, tag, (total, nt + n + 2), device_side=True)
+    views, off = [], 0
+    for a, length in parts:
+        if a is not None:
+            h_in.numpy()[off:off + length] = a.reshape(-1)
+        views.append(d_in[off:off + length])
+        off += length
+    d_in.copy_(h_in, non_blocking=True)
+    # info: 4 x int32 behind theta and the weights
+    launch(views, dict(theta=d_out[:nt], weights=d_out[nt:nt + n], info=d_out[nt + n:].view(torch.int32)))
+    h_out.copy_(d_out, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    res = h_out.numpy()
+    return res[:nt], res[nt:nt + n], res[nt + n:].view(np.int32), views
+
+
 def update_weights(losses, tol=1e-3, maxiter=100):
     '''Optimize Bernoulli probabilities (reference rlvi.py:8-20).'''
     return _roundtrip_f64(losses, lambda l: ops.update_weights_f64(l, tol=tol, maxiter=maxiter)[0])
@@ -131,22 +153,14 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, return_info=False):
     n, d = Xh.shape
     ws = ops.workspace(dev, n, 0)
     if n > 0 and d > 0 and ops.linear_regression_check(n, d):
-        h_in, h_out, d_in, d_out = _STAGE.get(dev, "linreg", (n * d + n, d + n + 2), device_side=True)
-        h_in.numpy()[:n * d] = Xh.reshape(-1)
-        h_in.numpy()[n * d:] = yh
-        d_in.copy_(h_in, non_blocking=True)
-        info = d_out[d + n:].view(torch.int32)              # 4 x int32 behind theta and the weights
-        ops.linear_regression(d_in[:n * d].view(n, d), d_in[n * d:], maxiter=maxiter, tol=tol,
-                              theta=d_out[:d], weights=d_out[d:d + n], info=info, ws=ws)
-        h_out.copy_(d_out, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()        # the one host wait of the call
-        res = h_out.numpy()
-        inf = res[d + n:].view(np.int32)
+        theta, w, inf, (Xd, yd) = _one_launch_roundtrip(
+            dev, "linreg", [(Xh, n * d), (yh, n)], d, n,
+            lambda v, out: ops.linear_regression(v[0].view(n, d), v[1], maxiter=maxiter, tol=tol, ws=ws, **out))
         if inf[3] == 0:
             if return_info:
-                return res[:d].copy(), res[d:d + n].copy(), int(inf[0])
-            return res[:d].copy()
-        Xd, yd = d_in[:n * d].view(n, d), d_in[n * d:]
+                return theta.copy(), w.copy(), int(inf[0])
+            return theta.copy()
+        Xd = Xd.view(n, d)
     else:
         Xd, yd = torch.from_numpy(Xh).to(dev), torch.from_numpy(yh).to(dev)
     theta, w, outer = _linear_regression_host_loop(Xd, yd, maxiter, tol)
@@ -200,25 +214,17 @@ def _logistic_regression_newton(X, y, maxiter, tol, return_info):
     dev = _dev()
     ws = ops.workspace(dev, n, 0)
     D = d + 1
-    h_in, h_out, d_in, d_out = _STAGE.get(dev, "logreg", (n * d + n, D + n + 2), device_side=True)
-    h_in.numpy()[:n * d] = Xh.reshape(-1)
-    h_in.numpy()[n * d:] = yh
-    d_in.copy_(h_in, non_blocking=True)
-    info = d_out[D + n:].view(torch.int32)                  # 4 x int32 behind theta and the weights
-    ops.logistic_regression(d_in[:n * d].view(n, d), d_in[n * d:], maxiter=maxiter, tol=tol, theta=d_out[:D],
-                            weights=d_out[D:D + n], info=info, ws=ws)
-    h_out.copy_(d_out, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()            # the one host wait of the call
-    res = h_out.numpy()
-    inf = res[D + n:].view(np.int32)
+    theta, w, inf, _ = _one_launch_roundtrip(
+        dev, "logreg", [(Xh, n * d), (yh, n)], D, n,
+        lambda v, out: ops.logistic_regression(v[0].view(n, d), v[1], maxiter=maxiter, tol=tol, ws=ws, **out))
     if inf[3] == 1:
         raise ValueError("logistic_regression: the fit met numbers that are not finite, or a pivot of its Newton "
                          "system that is not safely positive (a design scaled beyond what fp64 resolves)")
     if inf[3] == 2:
         ws.raise_on_status("logistic_regression", mask=_lib.ST_NOCONV)
     if return_info:
-        return res[:D].copy(), res[D:D + n].copy(), int(inf[0])
-    return res[:D].copy()
+        return theta.copy(), w.copy(), int(inf[0])
+    return theta.copy()
 
 
 def logistic_regression(X, y, maxiter=100, tol=1e-2, *, solver="liblinear", return_info=False):
@@ -295,23 +301,17 @@ def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None
     dev = _dev()
     ws = ops.workspace(dev, n, 0)
     nt = d * d if kind == "covariance" else d
-    h_in, h_out, d_in, d_out = _STAGE.get(dev, "moments_" + kind, (n * d + d, nt + n + 2), device_side=True)
-    h_in.numpy()[:n * d] = xh.reshape(-1)
-    if init is not None:
-        h_in.numpy()[n * d:] = init
-    d_in.copy_(h_in, non_blocking=True)
-    x_dev = d_in[:n * d].view(n, d)
-    out = dict(theta=d_out[:nt], weights=d_out[nt:nt + n], info=d_out[nt + n:].view(torch.int32), ws=ws)
-    if kind == "mean":
-        ops.robust_mean(x_dev, maxiter=maxiter, tol=tol, **out)
-    elif kind == "pca":
-        ops.robust_pca(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else d_in[n * d:], **out)
-    else:
-        ops.robust_covariance(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, **out)
-    h_out.copy_(d_out, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()            # the one host wait of the call
-    res = h_out.numpy()
-    inf = res[nt + n:].view(np.int32).copy()
+
+    def launch(v, out):
+        x_dev = v[0].view(n, d)
+        if kind == "mean":
+            ops.robust_mean(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
+        elif kind == "pca":
+            ops.robust_pca(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws, **out)
+        else:
+            ops.robust_covariance(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
+    theta, w, inf, _ = _one_launch_roundtrip(dev, "moments_" + kind, [(xh, n * d), (init, d)], nt, n, launch)
+    inf = inf.copy()
     if inf[3] == 1:
         if kind == "covariance":
             raise ValueError("Singular covariance matrix")   # utils.py:99-100
@@ -319,9 +319,9 @@ def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None
                          f"positive")
     if inf[3] == 2:
         ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
-    theta = res[:nt].copy().reshape((d, d) if kind == "covariance" else (d,))
+    theta = theta.copy().reshape((d, d) if kind == "covariance" else (d,))
     if return_info:
-        return theta, res[nt:nt + n].copy(), inf
+        return theta, w.copy(), inf
     return theta
 
 

@@ -1236,7 +1236,7 @@ def test_standard_and_online_mirrors_golden(golden, gpu, oracle):
 
 
 @pytest.mark.parametrize("n,d", [(40, 10), (1000, 20), (17, 1), (512, 15), (513, 16), (1024, 23), (1025, 24),
-                                 (3000, 31), (4096, 5), (64, 30), (200, 8)])
+                                 (3000, 31), (4096, 5), (64, 30), (200, 8), (1030, 14), (1100, 18)])
 def test_linear_regression_in_one_launch_vs_oracle(n, d, gpu, oracle):
     """rlvi_linear_regression_f64 (standard.hip): the whole estimator of rlvi.py:68-89 in one launch -- the stop
     test on the device, one host wait -- against the oracle's restatement (scipy lstsq + the pinned C E-step):
