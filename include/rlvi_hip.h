@@ -567,6 +567,43 @@ int rlvi_update_weights_constrained_f64(const double *losses, int64_t n, double 
                                         double *out, int32_t *info, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A Monte-Carlo sweep in ONE launch: `batch` independent problems of one shape, one workgroup each (the kernels above
+ * on a grid of `batch` workgroups; nothing waits for another workgroup, no cooperative launch).  The reference's
+ * experiments are such loops (standard-learning/main.py):
+ *   rlvi_linear_regression_batch_f64     main.py:261-273   20 corruption levels x 100 runs of 40 x 10
+ *   rlvi_logistic_regression_batch_f64   main.py:431-437   100 runs of 200 x 2
+ *   rlvi_robust_mean_batch_f64           main.py:180-188   20 x 100 runs of 100 x 2
+ *   rlvi_robust_pca_batch_f64            main.py:489-494   100 runs of 40 x 2, one theta_init for all
+ *   rlvi_robust_covariance_batch_f64     main.py:539-544   100 runs of 50 x 2, one eps for all
+ * The single entry's argument list with `batch` in front of n, the arrays contiguous with the problem as the slowest
+ * index: X / sample [batch, n, d], y [batch, n], theta [batch, nt] (nt = d; d + 1 logistic; d * d covariance), weights
+ * [batch, n], losses [batch, n] (logistic; may be NULL), info int32[batch, 4].  theta_init [d] (or NULL) and n_eff are
+ * shared by the whole batch.
+ *   Problem b gets EXACTLY the theta, weights and info the single entry gives for it alone: the same kernel template,
+ *   thread count, sums and dispatch by (n, d).  info[4 b + 3] is problem b's flag, with the single entry's meaning
+ *   (linear regression 1: the caller takes the general path for THAT problem; its rows of theta / weights are not
+ *   written).  RLVI_ST_NOCONV in the workspace is raised if ANY problem ends with flag 2.
+ * Validation is the single entry's, and batch <= 0 is RLVI_E_SHAPE, batch > 1 048 576 RLVI_E_LIMIT.  Graph-capturable
+ * as the single entries are.  A slice of a batch is 8-byte aligned, which is all the kernels ask of their fp64 arrays.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                     int maxiter, double tol, double estep_tol, int estep_maxiter, double *theta,
+                                     double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_logistic_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                       int maxiter, double tol, double estep_tol, int estep_maxiter, double C,
+                                       double *theta, double *weights, double *losses, int32_t *info, void *ws,
+                                       void *stream);
+int rlvi_robust_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter, double tol,
+                               double estep_tol, int estep_maxiter, double *theta, double *weights, int32_t *info,
+                               void *ws, void *stream);
+int rlvi_robust_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter, double tol,
+                              const double *theta_init, double estep_tol, int estep_maxiter, double *theta,
+                              double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_robust_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double n_eff,
+                                     int maxiter, double tol, double estep_tol, int estep_maxiter, double *theta,
+                                     double *weights, int32_t *info, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

@@ -99,6 +99,14 @@ SIGNATURES = {
     "rlvi_robust_pca_f64": (_int, [_vp, _i64, _i64, _int, _f64, _vp, _f64, _int, _vp, _vp, _vp, _vp, _vp]),
     "rlvi_robust_covariance_f64": (_int, [_vp, _i64, _i64, _f64, _int, _f64, _f64, _int, _vp, _vp, _vp, _vp, _vp]),
     "rlvi_update_weights_constrained_f64": (_int, [_vp, _i64, _f64, _f64, _int, _vp, _vp, _vp, _vp]),
+    "rlvi_linear_regression_batch_f64": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _f64, _f64, _int, _vp, _vp, _vp, _vp,
+                                                _vp]),
+    "rlvi_logistic_regression_batch_f64": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _f64, _f64, _int, _f64, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp]),
+    "rlvi_robust_mean_batch_f64": (_int, [_vp, _i64, _i64, _i64, _int, _f64, _f64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "rlvi_robust_pca_batch_f64": (_int, [_vp, _i64, _i64, _i64, _int, _f64, _vp, _f64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "rlvi_robust_covariance_batch_f64": (_int, [_vp, _i64, _i64, _i64, _f64, _int, _f64, _f64, _int, _vp, _vp, _vp,
+                                                _vp, _vp]),
     "rlvi_sample_weight_online_f64": (_int, [_vp, _vp, _f64, _int, _i64, _i64, _f64, _int, _vp, _vp, _vp, _vp]),
     "rlvi_stream_copy": (_int, [_vp, _vp, ctypes.c_size_t, _vp]),
 }

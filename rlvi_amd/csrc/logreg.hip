@@ -295,7 +295,12 @@ __device__ __forceinline__ int lg_fit(const LgShared &sh, const double *__restri
 
 // mode 0: the estimator (rlvi.py:92-108) -> theta [d + 1] = (intercept, coef), weights [n], losses (may be NULL);
 // mode 1: one fit with the caller's weights w_in (utils.py:61-73) -> theta, losses [n].
-template <int E, int DS, int NB>
+// BATCH (mode 0 only): workgroup b works on problem b of a contiguous batch (X [B, n, d], y [B, n], theta [B, d + 1],
+// weights [B, n], losses [B, n] or NULL, info [B, 4]) behind wave-uniform pointer offsets -- a template flag, as in
+// linreg_rlvi_kernel: the single form keeps its instructions.  `status` is the ONE word of the workspace for all
+// workgroups (atomicOr); a problem's own flag is info[4 b + 3].  Everything read from LDS is written by this
+// workgroup first (th and G here, th and zsh again by every fit, hsh / csh / gv / dl / rhs before their reads).
+template <int E, int DS, int NB, bool BATCH = false>
 __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
     const double *__restrict__ X, const double *__restrict__ y, const double *__restrict__ w_in, int n, int d,
     int npad, int mode, int maxiter, double tol, double etol, int emaxiter, double creg,
@@ -303,9 +308,18 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rlvi_kernel(
     int32_t *__restrict__ info, int32_t *__restrict__ status, unsigned long long *__restrict__ dbg) {
     extern __shared__ double sm[];
     LgShared sh;
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x;                   // (64-bit offsets: B n d passes 2^31)
+        X += b * (size_t)n * (size_t)d;
+        y += b * (size_t)n;
+        theta_out += b * (size_t)(d + 1);
+        w_out += b * (size_t)n;
+        if (losses_out != nullptr) losses_out += b * (size_t)n;
+        info += b * 4;
+    }
 #if RLVI_STAMPS
     sh.dbg = dbg;
-    sh.nst = 0;
+    sh.nst = (BATCH && blockIdx.x != 0) ? (1 << 30) : 0;      // only workgroup 0 leaves stamps
 #else
     (void)dbg;
 #endif
@@ -403,26 +417,29 @@ static int lg_check(int64_t n, int64_t d) {
     return (n <= SL_MAXN && d <= LG_MAXD) ? 0 : RLVI_E_LIMIT;
 }
 
+// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms
+template <bool BATCH = false>
 static int lg_launch(const double *X, const double *y, const double *w_in, int64_t n, int64_t d, int mode,
                      int maxiter, double tol, double etol, int emaxiter, double creg, double *theta, double *w_out,
-                     double *losses, int32_t *info, void *ws, hipStream_t st) {
+                     double *losses, int32_t *info, void *ws, hipStream_t st, int64_t batch = 1) {
     const int npad = (int)((n + 63) / 64) * 64;
     const size_t lds = lg_lds_doubles(npad) * sizeof(double);
     int32_t *status = &static_cast<WsHeader *>(ws)->status;
     auto go = [&](auto kern) {
         // (asked for per kernel: allow_dyn_lds keeps its once-per-device state by the kernel's address)
         if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, X, y, w_in, (int)n, (int)d, npad, mode, maxiter, tol,
-                      etol, emaxiter, creg, theta, w_out, losses, info, status, stamp_base(ws));
+        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, y, w_in, (int)n, (int)d,
+                      npad, mode, maxiter, tol, etol, emaxiter, creg, theta, w_out, losses, info, status,
+                      stamp_base(ws));
     };
     // samples per thread (1 / 4 / 16); the system of d + 1 unknowns solved padded to 4 / 16 / 24 / 32 rows; [X | 1]
     // and the gradient's column in one 16-column block (d <= 14) or two
 #define RLVI_LG(E_)                                                     \
     do {                                                                \
-        if (d <= 3) return go(logreg_rlvi_kernel<E_, 4, 1>);            \
-        if (d <= 14) return go(logreg_rlvi_kernel<E_, 16, 1>);          \
-        if (d <= 23) return go(logreg_rlvi_kernel<E_, 24, 2>);          \
-        return go(logreg_rlvi_kernel<E_, 32, 2>);                       \
+        if (d <= 3) return go(logreg_rlvi_kernel<E_, 4, 1, BATCH>);     \
+        if (d <= 14) return go(logreg_rlvi_kernel<E_, 16, 1, BATCH>);   \
+        if (d <= 23) return go(logreg_rlvi_kernel<E_, 24, 2, BATCH>);   \
+        return go(logreg_rlvi_kernel<E_, 32, 2, BATCH>);                \
     } while (0)
     if (n <= SL_THREADS) RLVI_LG(1);
     if (n <= 4 * SL_THREADS) RLVI_LG(4);
@@ -443,8 +460,20 @@ extern "C" int rlvi_logistic_regression_f64(const double *X, const double *y, in
     if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0 || !(C > 0.0)) return RLVI_E_SHAPE;
     if (lg_check(n, d)) return RLVI_E_LIMIT;
     if (sl_misaligned({X, y, theta, weights, losses}, info, ws)) return RLVI_E_ALIGN;
-    return lg_launch(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses, info,
+    return lg_launch<>(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses, info,
                      ws, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_logistic_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                                  int maxiter, double tol, double estep_tol, int estep_maxiter,
+                                                  double C, double *theta, double *weights, double *losses,
+                                                  int32_t *info, void *ws, void *stream) {
+    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
+    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0 || !(C > 0.0)) return RLVI_E_SHAPE;
+    if (batch > SL_MAXBATCH || lg_check(n, d)) return RLVI_E_LIMIT;
+    if (sl_misaligned({X, y, theta, weights, losses}, info, ws)) return RLVI_E_ALIGN;
+    return lg_launch<true>(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses,
+                           info, ws, static_cast<hipStream_t>(stream), batch);
 }
 
 extern "C" int rlvi_logistic_fit_f64(const double *X, const double *y, const double *w, int64_t n, int64_t d, double C,
@@ -453,6 +482,6 @@ extern "C" int rlvi_logistic_fit_f64(const double *X, const double *y, const dou
     if (n <= 0 || d <= 0 || !(C > 0.0)) return RLVI_E_SHAPE;
     if (lg_check(n, d)) return RLVI_E_LIMIT;
     if (sl_misaligned({X, y, w, theta, losses}, info, ws)) return RLVI_E_ALIGN;
-    return lg_launch(X, y, w, n, d, 1, 0, 0.0, 0.0, 0, C, theta, nullptr, losses, info, ws,
+    return lg_launch<>(X, y, w, n, d, 1, 0, 0.0, 0.0, 0, C, theta, nullptr, losses, info, ws,
                      static_cast<hipStream_t>(stream));
 }

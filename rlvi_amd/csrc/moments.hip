@@ -399,13 +399,25 @@ static size_t mo_lds_bytes(int64_t nd) { return (mo_slots_off(nd) + sl_slot_doub
 
 // MODE 0 / 1 / 2: mean / pca / covariance.  theta_out: [d], [d], [d * d]; info: { outer iterations, inner iterations of
 // the last E-step, inner iterations in all | Jacobi sweeps in all | E-steps with the constraint active, flag }.
-template <int MODE, int E, int DS>
+// BATCH: workgroup b works on problem b of a contiguous batch (X [B, n, d], theta [B, d] or [B, d * d], weights [B, n],
+// info [B, 4]; theta_init and n_eff are the whole batch's) behind wave-uniform pointer offsets -- a template flag, as
+// in linreg_rlvi_kernel: the single form keeps its instructions.  `status` is the ONE word of the workspace for all
+// workgroups (atomicOr); a problem's own flag is info[4 b + 3].  LDS holds the sample, staged by this workgroup, and the
+// slots, written before every read: nothing a CU's previous workgroup left behind is read.
+template <int MODE, int E, int DS, bool BATCH = false>
 __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
     const double *__restrict__ X, const double *__restrict__ theta_init, int n, int d, int maxiter, double tol,
     double etol, int emaxiter, double n_eff, double *__restrict__ theta_out, double *__restrict__ w_out,
     int32_t *__restrict__ info, int32_t *__restrict__ status) {
     extern __shared__ double sm[];
     constexpr int NT = MoTheta<MODE, DS>::N;
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x;                   // (64-bit offsets: B n d passes 2^31)
+        X += b * (size_t)n * (size_t)d;
+        theta_out += b * (size_t)(MODE == 2 ? d * d : d);
+        w_out += b * (size_t)n;
+        info += b * 4;
+    }
     MoShared sh;
     mo_carve(sh, sm, n * d);
     const int tid = threadIdx.x;
@@ -578,24 +590,25 @@ static int mo_check(int64_t n, int64_t d) {
     return (n >= 2 && n <= SL_MAXN && d <= MO_MAXD && n * d <= MO_MAXND) ? 0 : RLVI_E_LIMIT;
 }
 
-template <int MODE>
+// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms
+template <int MODE, bool BATCH = false>
 static int mo_launch(const double *X, const double *theta_init, int64_t n, int64_t d, int maxiter, double tol,
                      double etol, int emaxiter, double n_eff, double *theta, double *w_out, int32_t *info, void *ws,
-                     hipStream_t st) {
+                     hipStream_t st, int64_t batch = 1) {
     const size_t lds = mo_lds_bytes(n * d);
     int32_t *status = &static_cast<WsHeader *>(ws)->status;
     auto go = [&](auto kern) {
         // (asked for per kernel: allow_dyn_lds keeps its once-per-device state by the kernel's address)
         if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, X, theta_init, (int)n, (int)d, maxiter, tol, etol,
-                      emaxiter, n_eff, theta, w_out, info, status);
+        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, theta_init, (int)n, (int)d,
+                      maxiter, tol, etol, emaxiter, n_eff, theta, w_out, info, status);
     };
     // samples per thread (1 / 4 / 16); the d x d algebra padded to 2 / 4 / 8
 #define RLVI_MO(E_)                                                     \
     do {                                                                \
-        if (d <= 2) return go(moments_rlvi_kernel<MODE, E_, 2>);        \
-        if (d <= 4) return go(moments_rlvi_kernel<MODE, E_, 4>);        \
-        return go(moments_rlvi_kernel<MODE, E_, 8>);                    \
+        if (d <= 2) return go(moments_rlvi_kernel<MODE, E_, 2, BATCH>); \
+        if (d <= 4) return go(moments_rlvi_kernel<MODE, E_, 4, BATCH>); \
+        return go(moments_rlvi_kernel<MODE, E_, 8, BATCH>);             \
     } while (0)
     if (n <= SL_THREADS) RLVI_MO(1);
     if (n <= 4 * SL_THREADS) RLVI_MO(4);
@@ -604,10 +617,10 @@ static int mo_launch(const double *X, const double *theta_init, int64_t n, int64
 }
 
 static int mo_args(const double *sample, int64_t n, int64_t d, int maxiter, int estep_maxiter, const double *theta_init,
-                   double *theta, double *weights, int32_t *info, void *ws) {
+                   double *theta, double *weights, int32_t *info, void *ws, int64_t batch = 1) {
     if (sl_any_null({sample, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
-    if (mo_check(n, d)) return RLVI_E_LIMIT;
+    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
+    if (batch > SL_MAXBATCH || mo_check(n, d)) return RLVI_E_LIMIT;
     return sl_misaligned({sample, theta_init, theta, weights}, info, ws) ? RLVI_E_ALIGN : 0;
 }
 
@@ -639,6 +652,32 @@ extern "C" int rlvi_robust_covariance_f64(const double *sample, int64_t n, int64
     if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws)) return e;
     return mo_launch<2>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta, weights, info, ws,
                         static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_robust_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter,
+                                          double tol, double estep_tol, int estep_maxiter, double *theta,
+                                          double *weights, int32_t *info, void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws, batch)) return e;
+    return mo_launch<0, true>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights, info,
+                              ws, static_cast<hipStream_t>(stream), batch);
+}
+
+extern "C" int rlvi_robust_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter,
+                                         double tol, const double *theta_init, double estep_tol, int estep_maxiter,
+                                         double *theta, double *weights, int32_t *info, void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, theta_init, theta, weights, info, ws, batch))
+        return e;
+    return mo_launch<1, true>(sample, theta_init, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights,
+                              info, ws, static_cast<hipStream_t>(stream), batch);
+}
+
+extern "C" int rlvi_robust_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double n_eff,
+                                                int maxiter, double tol, double estep_tol, int estep_maxiter,
+                                                double *theta, double *weights, int32_t *info, void *ws,
+                                                void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws, batch)) return e;
+    return mo_launch<2, true>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta, weights,
+                              info, ws, static_cast<hipStream_t>(stream), batch);
 }
 
 extern "C" int rlvi_update_weights_constrained_f64(const double *losses, int64_t n, double n_eff, double tol,

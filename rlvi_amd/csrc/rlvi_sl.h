@@ -6,7 +6,10 @@
 //     Gram partials into it (sl_gram_collect), the pivot floor and the L D L^T solve on one wave (sl_ldlt_solve);
 //   * the E-step's fixed point on the threads' own samples (sl_estep_fixed_point) and the outer stop test
 //     (sl_theta_moved);
-//   * the argument checks of the extern "C" entries (sl_any_null, sl_misaligned).
+//   * the argument checks of the extern "C" entries (sl_any_null, sl_misaligned) and the batch forms' limit
+//     (SL_MAXBATCH: the estimator kernels as `template <..., bool BATCH>`, workgroup b on problem b of a contiguous
+//     batch behind pointer offsets at kernel entry; a slice of a batch is 8-byte aligned, which is what every fp64
+//     load of these kernels -- all of them scalar doubles -- and sl_misaligned ask).
 // linreg_rlvi_kernel (standard.hip) is held to the instructions it had: it takes the offsets, the pivot floor and
 // sl_block_sum2 from here and keeps the Gram collection, the solve, the fixed point and the stop test in place --
 // each of them called from here moves its register allocation, and single cells of its sweep by up to 2 % either way
@@ -27,6 +30,7 @@ constexpr int SL_THREADS = 256;
 constexpr int SL_NW = SL_THREADS / WAVE;
 constexpr int SL_DP = 32;                         // the design padded to two 16-column blocks
 constexpr int SL_MAXN = 4096;                     // samples the one-workgroup form takes (16 per thread)
+constexpr int64_t SL_MAXBATCH = 1 << 20;          // problems of one batch launch (one workgroup each)
 constexpr int SL_GPITCH = SL_DP + 1;
 constexpr double SL_EPS = 2.220446049250313e-16;
 

@@ -359,16 +359,29 @@ __device__ __forceinline__ double sl_residuals(const SlShared &sh, const double 
     return num / den;
 }
 
-template <int E, int DS, int NB, bool RES>
+// BATCH: workgroup b works on problem b of a contiguous batch (X [B, n, d], y [B, n], theta [B, d], weights [B, n],
+// info [B, 4]) -- the same code behind wave-uniform pointer offsets, so a problem gets the bits of the single launch;
+// a template flag, not arithmetic on blockIdx.x in the one kernel: the single form keeps its instructions
+// (profiles/r18_batch.md).  Everything read from LDS is written by this workgroup first (wsh, th, G below; rsh, red,
+// rhs, LT, the slots and flag before their first read): a CU's previous workgroup leaves nothing behind that counts.
+template <int E, int DS, int NB, bool RES, bool BATCH = false>
 __global__ __launch_bounds__(SL_THREADS) void linreg_rlvi_kernel(
     const double *__restrict__ X, const double *__restrict__ y, int n, int d, int npad, int maxiter, double tol,
     double etol, int emaxiter, double *__restrict__ theta_out, double *__restrict__ w_out,
     int32_t *__restrict__ info, unsigned long long *__restrict__ dbg) {
     extern __shared__ double sm[];
     SlShared sh;
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x;                   // (64-bit offsets: B n d passes 2^31)
+        X += b * (size_t)n * (size_t)d;
+        y += b * (size_t)n;
+        theta_out += b * (size_t)d;
+        w_out += b * (size_t)n;
+        info += b * 4;
+    }
 #if RLVI_STAMPS
     sh.dbg = dbg;
-    sh.nst = 0;
+    sh.nst = (BATCH && blockIdx.x != 0) ? (1 << 30) : 0;      // only workgroup 0 leaves stamps
 #else
     (void)dbg;
 #endif
@@ -634,14 +647,11 @@ extern "C" int rlvi_linear_regression_check(int64_t n, int64_t d) {
     return (n <= SL_MAXN && d < SL_DP) ? 0 : RLVI_E_LIMIT;
 }
 
-extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
-                                          double tol, double estep_tol, int estep_maxiter, double *theta,
-                                          double *weights, int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
-    if (n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+// the launch of a checked call: one workgroup, or (BATCH) one per problem -- ONE dispatch rule for both forms
+template <bool BATCH>
+static int sl_linreg_launch(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, int maxiter,
+                            double tol, double estep_tol, int estep_maxiter, double *theta, double *weights,
+                            int32_t *info, void *ws, hipStream_t st) {
     // (samples per thread: four up to n = 1024, sixteen beyond; the system solved padded to 12 / 16 / 20 / 24 / 32 rows;
     //  one or two 16-column blocks of [X | y]; the design resident on the chip -- registers + LDS -- when n <= 1024
     //  and d <= 23)
@@ -651,22 +661,45 @@ extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int6
     const size_t lds = sl_lds_doubles(npad_x, res && two) * sizeof(double);
     auto go = [&](auto kern) {
         if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d, npad_x, maxiter, tol,
-                      estep_tol, estep_maxiter, theta, weights, info,
+        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d,
+                      npad_x, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info,
                       reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF));
     };
     if (res) {
-        if (d <= 12) return go(linreg_rlvi_kernel<4, 12, 1, true>);
-        if (d <= 15) return go(linreg_rlvi_kernel<4, 16, 1, true>);
-        if (d <= 20) return go(linreg_rlvi_kernel<4, 20, 2, true>);
-        return go(linreg_rlvi_kernel<4, 24, 2, true>);
+        if (d <= 12) return go(linreg_rlvi_kernel<4, 12, 1, true, BATCH>);
+        if (d <= 15) return go(linreg_rlvi_kernel<4, 16, 1, true, BATCH>);
+        if (d <= 20) return go(linreg_rlvi_kernel<4, 20, 2, true, BATCH>);
+        return go(linreg_rlvi_kernel<4, 24, 2, true, BATCH>);
     }
-    if (n <= 4 * SL_THREADS) return go(linreg_rlvi_kernel<4, 32, 2, false>);      // d = 24 .. 31
-    if (d <= 12) return go(linreg_rlvi_kernel<16, 12, 1, false>);
-    if (d <= 15) return go(linreg_rlvi_kernel<16, 16, 1, false>);
-    if (d <= 20) return go(linreg_rlvi_kernel<16, 20, 2, false>);
-    if (d <= 24) return go(linreg_rlvi_kernel<16, 24, 2, false>);
-    return go(linreg_rlvi_kernel<16, 32, 2, false>);
+    if (n <= 4 * SL_THREADS) return go(linreg_rlvi_kernel<4, 32, 2, false, BATCH>);      // d = 24 .. 31
+    if (d <= 12) return go(linreg_rlvi_kernel<16, 12, 1, false, BATCH>);
+    if (d <= 15) return go(linreg_rlvi_kernel<16, 16, 1, false, BATCH>);
+    if (d <= 20) return go(linreg_rlvi_kernel<16, 20, 2, false, BATCH>);
+    if (d <= 24) return go(linreg_rlvi_kernel<16, 24, 2, false, BATCH>);
+    return go(linreg_rlvi_kernel<16, 32, 2, false, BATCH>);
+}
+
+extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
+                                          double tol, double estep_tol, int estep_maxiter, double *theta,
+                                          double *weights, int32_t *info, void *ws, void *stream) {
+    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
+    if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
+    if (n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
+    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
+    return sl_linreg_launch<false>(X, y, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
+                                   static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                                int maxiter, double tol, double estep_tol, int estep_maxiter,
+                                                double *theta, double *weights, int32_t *info, void *ws,
+                                                void *stream) {
+    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
+    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
+    if (batch > SL_MAXBATCH || n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
+    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
+    return sl_linreg_launch<true>(X, y, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
+                                  static_cast<hipStream_t>(stream));
 }
 
 extern "C" int rlvi_sample_weight_online_f64(const double *X, const double *w, double b, int first, int64_t n,

@@ -545,14 +545,16 @@ def _one_launch(entry, inputs, args, outs, info, ws):
     """The call of a one-launch fp64 estimator on inputs its wrapper has checked:
     entry(*inputs, *inputs[0].shape, *args, *outs, info, ws, stream).  outs: one (tensor, elements) per output array;
     a tensor that is None is allocated here with that many elements -- or, with elements None as well, passed as
-    NULL (an optional output).  info and the workspace are made when not given.  Returns (*outs, info)."""
+    NULL (an optional output).  info and the workspace are made when not given.  Returns (*outs, info).
+    A batch entry: inputs[0] is [B, n, d], so that B travels in front of n, and info is int32[B, 4]."""
     L = _lib.load()
     X = inputs[0]
+    batched = X.dim() == 3
     outs = [torch.empty(numel, dtype=torch.float64, device=X.device) if t is None and numel is not None else t
             for t, numel in outs]
     if info is None:
-        info = torch.zeros(4, dtype=torch.int32, device=X.device)
-    ws = ws or workspace(X.device, X.shape[0], 0)
+        info = torch.zeros((X.shape[0], 4) if batched else 4, dtype=torch.int32, device=X.device)
+    ws = ws or workspace(X.device, X.shape[1 if batched else 0], 0)
     _lib.check(getattr(L, entry)(*(_ptr(t) for t in inputs), *X.shape, *args, *(_ptr(t) for t in outs), _ptr(info),
                                  ws.ptr, _stream_ptr()), entry)
     return (*outs, info)
@@ -665,6 +667,97 @@ def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, este
         (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
         ((None if theta is None else theta.view(-1), d * d), (weights, n)), info, ws)
     return theta.view(d, d), weights, info
+
+
+# ---- a Monte-Carlo sweep in ONE launch: B problems of one shape, one workgroup each.  The single forms' keywords; the
+# arrays carry a leading batch dimension; problem b gets the bits of the single call on it alone.
+def _batch_shape(what, X, *vectors):
+    """(B, n, d) of a batch [B, n, d] and its [B, n] vectors, all contiguous fp64 device tensors"""
+    _require_gpu(X, *vectors)
+    if not _fp64(X, dims=3):
+        raise ValueError(f"{what} [B, n, d] must be a contiguous fp64 device tensor")
+    if not all(_fp64(v, dims=2) and tuple(v.shape) == tuple(X.shape[:2]) for v in vectors):
+        raise ValueError(f"y must be a contiguous fp64 device tensor of {what}'s [B, n]")
+    return X.shape
+
+
+def _batch_outs(B, *outs):
+    """[(tensor or None, rows' length)] -> _one_launch's outs, a given tensor checked to be [B, length] elements"""
+    res = []
+    for t, k in outs:
+        if t is not None:
+            _require_gpu(t)
+            if not _fp64(t, numel=B * k):
+                raise ValueError(f"an output must be a contiguous fp64 device tensor of {B} x {k} elements")
+        res.append((t, B * k))
+    return res
+
+
+def linear_regression_batch(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None,
+                            weights=None, info=None, ws=None):
+    """B linear regressions (linear_regression above; the loop of standard-learning/main.py:261-273) as ONE launch
+    (rlvi_linear_regression_batch_f64): X [B, n, d], y [B, n] -> (theta [B, d], weights [B, n], info int32[B, 4]).
+    info[b, 3] == 1: problem b is rank-deficient, its rows were not written -- the general path is the caller's."""
+    B, n, d = _batch_shape("X", X, y)
+    theta, weights, info = _one_launch("rlvi_linear_regression_batch_f64", (X, y),
+                                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, C=100.0, theta=None,
+                              weights=None, losses=None, info=None, ws=None):
+    """B logistic regressions (logistic_regression above; main.py:431-437) as ONE launch
+    (rlvi_logistic_regression_batch_f64): X [B, n, d], y [B, n] -> (theta [B, d + 1], weights [B, n], info
+    int32[B, 4]); `losses` [B, n], if given, receives the last fits'."""
+    B, n, d = _batch_shape("X", X, y)
+    if losses is not None:
+        (losses, _), = _batch_outs(B, (losses, n))
+    theta, weights, _, info = _one_launch(
+        "rlvi_logistic_regression_batch_f64", (X, y),
+        (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter), float(C)),
+        _batch_outs(B, (theta, d + 1), (weights, n)) + [(losses, None)], info, ws)
+    return theta.view(B, d + 1), weights.view(B, n), info.view(B, 4)
+
+
+def robust_mean_batch(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None,
+                      info=None, ws=None):
+    """B robust means (robust_mean above; main.py:180-188) as ONE launch (rlvi_robust_mean_batch_f64): sample
+    [B, n, d] -> (theta [B, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    theta, weights, info = _one_launch("rlvi_robust_mean_batch_f64", (sample,),
+                                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def robust_pca_batch(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, estep_maxiter=100, theta=None,
+                     weights=None, info=None, ws=None):
+    """B robust PCAs (robust_pca above; main.py:489-494) as ONE launch (rlvi_robust_pca_batch_f64): sample [B, n, d],
+    theta_init [d] for all of them (or None) -> (theta [B, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    if theta_init is not None:
+        _require_gpu(theta_init)
+        if not _fp64(theta_init, numel=d):
+            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
+    theta, weights, info = _one_launch(
+        "rlvi_robust_pca_batch_f64", (sample,),
+        (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)),
+        _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def robust_covariance_batch(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, theta=None,
+                            weights=None, info=None, ws=None):
+    """B robust covariances (robust_covariance above; main.py:539-544) as ONE launch
+    (rlvi_robust_covariance_batch_f64): sample [B, n, d], one n_eff = n (1 - eps) for all of them -> (theta
+    [B, d, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    theta, weights, info = _one_launch(
+        "rlvi_robust_covariance_batch_f64", (sample,),
+        (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+        _batch_outs(B, (theta, d * d), (weights, n)), info, ws)
+    return theta.view(B, d, d), weights.view(B, n), info.view(B, 4)
 
 
 def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, info=None, ws=None):

@@ -6,6 +6,8 @@
                                                                (one_launch=True: one launch each, moments.hip)
     linear_regression(X, y, maxiter=100, tol=1e-3) -> theta    reference rlvi.py:68-89
     logistic_regression(X, y, maxiter=100, tol=1e-2) -> theta  reference rlvi.py:92-108
+    linear_regression_batch / logistic_regression_batch /      the Monte-Carlo loops of reference main.py:170-572:
+    mean_batch / pca_batch / covariance_batch                  B problems of one shape in ONE launch
 
 The E-step fixed point and the per-sample NLL (the X.theta contraction) run in
 librlvi_gfx950.so, and so does the weighted least-squares solve of linear_regression (normal
@@ -81,13 +83,15 @@ def _roundtrip_f64(host_in, fn):
     return h_out.numpy().copy().reshape(shape)
 
 
-def _one_launch_roundtrip(dev, tag, parts, nt, n, launch):
+def _one_launch_roundtrip(dev, tag, parts, nt, n, launch, batch=1):
     """The numpy-in / numpy-out call of a one-launch estimator: the host arrays `parts` = [(array or None, length)]
     packed into ONE pinned buffer and copied to the device, launch(device views of the parts, dict(theta [nt],
     weights [n], info int32[4])), ONE pinned copy of {theta, weights, info} back and the one host wait of the call.
-    Returns (theta, weights, info) as views of the pinned result -- copy what is handed out -- and the device views."""
+    Returns (theta, weights, info) as views of the pinned result -- copy what is handed out -- and the device views.
+    batch = B: the batch forms, whose theta, weights and info are B rows of nt, n and 4 (returned flat)."""
     total = sum(length for _, length in parts)
-    h_in, h_out, d_in, d_out = _STAGE.get(dev, tag, (total, nt + n + 2), device_side=True)
+    nt, n = batch * nt, batch * n
+    h_in, h_out, d_in, d_out = _STAGE.get(dev, tag, (total, nt + n + 2 * batch), device_side=True)
     views, off = [], 0
     for a, length in parts:
         if a is not None:
@@ -418,3 +422,169 @@ def covariance(sample, eps, maxiter=100, tol=1e-2, *, one_launch=False, return_i
         if np.linalg.norm(theta - prev, ord='fro') / np.linalg.norm(prev, ord='fro') <= tol:
             break
     return theta
+
+
+# ---- a Monte-Carlo sweep in ONE launch (the loops of standard-learning/main.py:170-572): B problems of one shape
+# stacked on a leading dimension, one workgroup each; problem b gets the bits of the single one-launch call on it alone.
+# One pinned H2D copy of the whole batch, ONE launch, one pinned D2H copy of {theta, weights, info}, one host wait --
+# never a loop of single calls: a shape beyond the one-launch limits raises RlviError.
+def _batch_inputs(what, X, y=None, nonfinite="Input contains NaN or infinity."):
+    """[B, n, d] (and y [B, n]) as contiguous fp64 host arrays, all finite: a problem that is not raises what the
+    single form raises for it, with its index, before anything reaches the device."""
+    Xh = np.ascontiguousarray(X, dtype=np.float64)
+    if Xh.ndim != 3:
+        raise ValueError(f"{what} must be [B, n, d]")
+    B, n, d = Xh.shape
+    yh = None
+    if y is not None:
+        yh = np.ascontiguousarray(y, dtype=np.float64)
+        if yh.shape != (B, n):
+            raise ValueError("X must be [B, n, d] and y [B, n]")
+    if B == 0:
+        raise ValueError(f"{what} holds no problem (B = 0)")
+    fin = np.isfinite(Xh).reshape(B, -1).all(axis=1)
+    if yh is not None:
+        fin &= np.isfinite(yh).all(axis=1)
+    if not fin.all():
+        raise ValueError(f"{nonfinite} (problem {int(np.argmin(fin))})")
+    return Xh, yh, B, n, d
+
+
+def _batch_flags(kind, ws, inf, return_info, flag1):
+    """The per-problem flags of a batch: what the single call raises for the lowest flagged problem, naming it -- or,
+    with return_info, nothing (the caller blanks the flagged rows; info says which).  The sticky NOCONV word that a
+    flag 2 raised is cleared either way."""
+    flagged = np.flatnonzero(inf[:, 3] != 0)
+    if flagged.size == 0:
+        return
+    b = int(flagged[0])
+    if return_info or inf[b, 3] == 1:
+        if (inf[:, 3] == 2).any():
+            ws.clear_status()
+        if return_info:
+            return
+        raise ValueError(f"{flag1} (problem {b})")
+    try:
+        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
+    except _lib.RlviError as e:
+        raise _lib.RlviError(f"{e} (problem {b})") from None
+
+
+def _batch_results(theta, w, inf, B, theta_shape, n, return_info):
+    theta, w = theta.copy().reshape((B,) + theta_shape), w.copy().reshape(B, n)
+    if not return_info:
+        return theta
+    bad = inf[:, 3] != 0
+    theta[bad] = np.nan
+    w[bad] = np.nan
+    return theta, w, inf
+
+
+def linear_regression_batch(X, y, maxiter=100, tol=1e-3, return_info=False):
+    """B calls of linear_regression (the sweep of main.py:261-273) as ONE launch: X [B, n, d], y [B, n] -> theta
+    [B, d].  n <= 4096, d <= 31 (RlviError beyond).  A problem the launch reports as rank-deficient (info[b, 3] == 1)
+    is recomputed by the general path on its device slice, as the single call does.  return_info: (theta, weights
+    [B, n], info int32[B, 4]); a recomputed problem's row of info is {its outer iterations, 0, 0, 1}."""
+    # (the single call meets a NaN on the device and raises this from its general path; a batch says so up front)
+    Xh, yh, B, n, d = _batch_inputs("X", X, y, nonfinite="array must not contain infs or NaNs")
+    if B == 0 or n == 0 or d == 0 or not ops.linear_regression_check(n, d):
+        raise _lib.RlviError(f"linear_regression_batch takes B >= 1 problems of n <= 4096 samples and 1 <= d <= 31 "
+                             f"features in its one launch: got B = {B}, n = {n}, d = {d}")
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, (Xd, yd) = _one_launch_roundtrip(
+        dev, "linreg_batch", [(Xh, B * n * d), (yh, B * n)], d, n,
+        lambda v, out: ops.linear_regression_batch(v[0].view(B, n, d), v[1].view(B, n), maxiter=maxiter, tol=tol,
+                                                   ws=ws, **out), batch=B)
+    theta, w, inf = theta.copy().reshape(B, d), w.copy().reshape(B, n), inf.copy().reshape(B, 4)
+    for b in np.flatnonzero(inf[:, 3] == 1):
+        th_b, w_b, outer = _linear_regression_host_loop(Xd.view(B, n, d)[b], yd.view(B, n)[b], maxiter, tol)
+        theta[b] = th_b.cpu().numpy()
+        if not np.isfinite(theta[b]).all():
+            ws.clear_status()
+            raise ValueError(f"array must not contain infs or NaNs (problem {int(b)})")     # as linear_regression
+        ws.raise_on_status(f"linear_regression_batch (problem {int(b)})", mask=_lib.ST_TIMEOUT | _lib.ST_NOCONV)
+        w[b] = w_b.cpu().numpy()
+        inf[b] = (outer, 0, 0, 1)
+    if return_info:
+        return theta, w, inf
+    return theta
+
+
+def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, return_info=False):
+    """B calls of logistic_regression(solver="newton") (main.py:431-437) as ONE launch: X [B, n, d], y [B, n] of 0 / 1
+    with both classes in every problem -> theta [B, d + 1].  n <= 4096, d <= 30 (RlviError beyond).  return_info:
+    (theta, weights [B, n], info int32[B, 4]); nothing is raised for a problem's flag then, its rows are NaN."""
+    Xh, yh, B, n, d = _batch_inputs("X", X, y)
+    if not np.isin(yh, (0.0, 1.0)).all():
+        b = int(np.argmin(np.isin(yh, (0.0, 1.0)).all(axis=1)))
+        raise ValueError(f"y must hold the class labels 0 and 1 (problem {b})")
+    if n == 0 or (yh.min(axis=1) == yh.max(axis=1)).any():
+        b = 0 if n == 0 else int(np.argmax(yh.min(axis=1) == yh.max(axis=1)))
+        raise ValueError(f"This solver needs samples of at least 2 classes in the data (problem {b})")
+    if d == 0 or not ops.logistic_regression_check(n, d):
+        raise _lib.RlviError(f"logistic_regression_batch takes n <= 4096 samples and 1 <= d <= 30 features in its one "
+                             f"launch: got n = {n}, d = {d}")
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, _ = _one_launch_roundtrip(
+        dev, "logreg_batch", [(Xh, B * n * d), (yh, B * n)], d + 1, n,
+        lambda v, out: ops.logistic_regression_batch(v[0].view(B, n, d), v[1].view(B, n), maxiter=maxiter, tol=tol,
+                                                     ws=ws, **out), batch=B)
+    inf = inf.copy().reshape(B, 4)
+    _batch_flags("logistic_regression_batch", ws, inf, return_info,
+                 "logistic_regression: the fit met numbers that are not finite, or a pivot of its Newton system that "
+                 "is not safely positive (a design scaled beyond what fp64 resolves)")
+    return _batch_results(theta, w, inf, B, (d + 1,), n, return_info)
+
+
+def _moments_batch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None):
+    xh, _, B, n, d = _batch_inputs("sample", sample)
+    init = None if theta_init is None else np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
+    if init is not None and init.shape[0] != d:
+        raise ValueError("theta_init must have the samples' d elements")
+    if init is not None and not np.isfinite(init).all():
+        raise ValueError("Input contains NaN or infinity.")
+    if kind == "covariance" and not 0.0 < eps < 1.0:
+        raise ValueError(f"covariance_batch needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
+    if n == 0 or d == 0 or not ops.moments_check(n, d):
+        raise _lib.RlviError(f"{kind}_batch takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with n d <= 16384 "
+                             f"in its one launch: got n = {n}, d = {d}")
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    shape = (d, d) if kind == "covariance" else (d,)
+
+    def launch(v, out):
+        x_dev = v[0].view(B, n, d)
+        if kind == "mean":
+            ops.robust_mean_batch(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
+        elif kind == "pca":
+            ops.robust_pca_batch(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws,
+                                 **out)
+        else:
+            ops.robust_covariance_batch(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
+    theta, w, inf, _ = _one_launch_roundtrip(dev, "moments_batch_" + kind, [(xh, B * n * d), (init, d)],
+                                             int(np.prod(shape)), n, launch, batch=B)
+    inf = inf.copy().reshape(B, 4)
+    _batch_flags(kind + "_batch", ws, inf, return_info,
+                 "Singular covariance matrix" if kind == "covariance" else
+                 f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely positive")
+    return _batch_results(theta, w, inf, B, shape, n, return_info)
+
+
+def mean_batch(sample, maxiter=100, tol=1e-3, return_info=False):
+    """B calls of mean(one_launch=True) (main.py:180-188) as ONE launch: sample [B, n, d] -> theta [B, d]; limits and
+    return_info as for mean, info int32[B, 4]; with return_info a flagged problem's rows are NaN, nothing is raised."""
+    return _moments_batch("mean", sample, maxiter, tol, return_info)
+
+
+def pca_batch(sample, maxiter=100, tol=1e-2, theta_init=None, return_info=False):
+    """B calls of pca(one_launch=True) (main.py:489-494) as ONE launch: sample [B, n, d], ONE theta_init [d] for all
+    problems (as in the reference's loop) -> theta [B, d]."""
+    return _moments_batch("pca", sample, maxiter, tol, return_info, theta_init=theta_init)
+
+
+def covariance_batch(sample, eps, maxiter=100, tol=1e-2, return_info=False):
+    """B calls of covariance(one_launch=True) (main.py:539-544) as ONE launch: sample [B, n, d], ONE eps for all
+    problems -> theta [B, d, d]."""
+    return _moments_batch("covariance", sample, eps=eps, maxiter=maxiter, tol=tol, return_info=return_info)
