@@ -604,6 +604,49 @@ int rlvi_robust_covariance_batch_f64(const double *sample, int64_t batch, int64_
                                      double *weights, int32_t *info, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Robust Risk Minimization (standard-learning/rrm.py, Osama et al. 2020), the competitor the reference's experiments
+ * fit on the same sample (main.py:184, :222, :492, :542): mean, pca and covariance as ONE launch each, their batch forms
+ * and the weight rule on its own (moments.hip).  The kernels, fits, limits and flags of the rlvi_robust_* entries
+ * above; what differs:
+ *   rlvi_rrm_update_weights_f64   rrm.py:12-33: out_i = exp(-l_i / alpha) / sum_j exp(-l_j / alpha) at the alpha that
+ *               minimises alpha (log sum_i exp(-l_i / alpha) - log((1 - eps) n)).  The reference hands that to scipy's
+ *               minimize_scalar over xi = log alpha; here xi is the exact root of the stationarity condition
+ *               "entropy of out = log((1 - eps) n)" (a bracket grown geometrically, then safeguarded Newton, at most
+ *               200 evaluations): the contract is the root, not Brent's iterate.  The losses are shifted by their
+ *               minimum (out does not change, nothing overflows) and the reference's floor of 1e-16 under every
+ *               exponential is dropped.  If the samples tied at the minimum, m of them, are (1 - eps) n or more there is
+ *               no root: out = 1 / m on them and 0 elsewhere, the limit alpha -> 0.  n <= 4096.
+ *               info = { evaluations, 0, 1 if there was a root, flag }.
+ *   rlvi_rrm_mean_f64         rrm.py:36-52: weights = 1 / n, theta = sum w x / sum w, losses = ||theta - x||^2 (no
+ *               variance), then up to `maxiter` times { update_weights(losses, eps), theta and losses again, stop when
+ *               ||theta - prev|| / ||prev|| <= tol }.
+ *   rlvi_rrm_pca_f64          rrm.py:94-107 with utils.py:76-89: the fit and the losses of rlvi_robust_pca_f64.
+ *   rlvi_rrm_covariance_f64   rrm.py:110-124 with utils.py:92-108: the fit and the losses of rlvi_robust_covariance_f64.
+ *   rlvi_rrm_*_batch_f64      the loops of main.py:180-188, :489-494, :539-544 around them: `batch` in front of n, the
+ *               arrays as for rlvi_robust_*_batch_f64, one eps (and theta_init) for all problems; problem b gets
+ *               exactly the bits of the single entry.
+ * eps takes the place of n_eff; there is no estep_tol / estep_maxiter.  info int32[4] = { outer iterations,
+ * evaluations of the last root-find, count, flag }, count = mean, covariance: evaluations in all; pca: Jacobi sweeps in
+ * all.  flag 1, NOTHING written: eps outside (0, 1), (1 - eps) n <= 1, a sample or a loss that is not finite, and
+ * what the fits flag.  flag 2: the root-find cap or the Jacobi cap (RLVI_ST_NOCONV in the workspace).
+ * ------------------------------------------------------------------------------------- */
+int rlvi_rrm_mean_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol, double *theta,
+                      double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_pca_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
+                     const double *theta_init, double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_covariance_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
+                            double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
+                            double tol, double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
+                           double tol, const double *theta_init, double *theta, double *weights, int32_t *info,
+                           void *ws, void *stream);
+int rlvi_rrm_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
+                                  double tol, double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_update_weights_f64(const double *losses, int64_t n, double eps, double *out, int32_t *info, void *ws,
+                                void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

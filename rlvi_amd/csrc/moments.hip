@@ -6,6 +6,14 @@
 //   rlvi_robust_covariance_f64             rlvi.py:128-144, utils.py:92-108    covariance(sample, eps, maxiter, tol)
 //   rlvi_update_weights_constrained_f64    rlvi.py:23-43                       update_weights_constrained(losses, n_eff)
 //
+// and the same three under Robust Risk Minimization (standard-learning/rrm.py), the competitor the reference's
+// experiments plot beside them: the outer loops above with another weight rule (mo_estep_rrm) and 1 / n as first weights:
+//
+//   rlvi_rrm_mean_f64                      standard-learning/rrm.py:36-52      mean(sample, eps, maxiter, tol)
+//   rlvi_rrm_pca_f64                       rrm.py:94-107, utils.py:76-89       pca(sample, eps, maxiter, tol, theta_init)
+//   rlvi_rrm_covariance_f64                rrm.py:110-124, utils.py:92-108     covariance(sample, eps, maxiter, tol)
+//   rlvi_rrm_update_weights_f64            rrm.py:12-33                        update_weights(losses, eps)
+//
 // The reference runs them on 100 x 2, 40 x 2 and 50 x 2 samples for 2 .. 8 outer iterations: latency that a launch, a
 // copy or a third-party call per statement can never amortise (DESIGN, "Mean, PCA and covariance in one launch").
 //
@@ -36,6 +44,8 @@ constexpr int MO_KMAX = 36;                        // values of one block sum: t
 constexpr int MO_JACOBI_CAP = 30;                  // sweeps of one eigen-solve
 constexpr int MO_ROOT_CAP = 200;                   // evaluations of one root-find
 constexpr double MO_EPS = SL_EPS;
+constexpr double MO_XI_MIN = -700.0, MO_XI_MAX = 700.0;   // xi = log alpha of the RRM rule: alpha stays a normal number
+constexpr double MO_TMAX = 800.0;                  // exp(-800) is 0: a larger l / alpha is cut here (phi t = 0, never 0 inf)
 
 struct MoShared {
     const double *xs;   // [n * d] the sample
@@ -150,13 +160,17 @@ template <int MODE, int DS> struct MoTheta { static constexpr int N = MODE == 2 
 
 // One M-step: theta from the weights w of this thread's samples, and their losses l.
 //   MODE 0  rlvi.py:48-51 / :56-59     theta = sum w x / sum w, r = ||theta - x||^2, losses = 1/2 r / (sum w r / sum w)
+//           RRM (rrm.py:38-39 / :45-46): losses = r, no variance
 //   MODE 1  utils.py:76-89             theta = first principal component of the rows w x (skipped: `given`, theta is
 //                                      the caller's), losses = ||x||^2 - (x.theta)^2
+//           RRM: (x.theta)^2 is rounded before it is subtracted, never fused into the subtraction -- at d = 1 the loss
+//           is then exactly 0, as it is in exact arithmetic, and not the product's rounding error: RRM's rule is
+//           scale-free, and would turn that noise into weights
 //   MODE 2  utils.py:92-108            theta = the weighted covariance (lower triangle), losses = 1/2 ((x - mu)^T
 //                                      C^-1 (x - mu) + log det C + d log 2 pi)
 // Returns, on every thread, 0, 1 (numbers that are not finite, no positive weight, a variance or a pivot not safely
 // positive) or 2 (the Jacobi cap).  All threads call.
-template <int MODE, int E, int DS>
+template <int MODE, int E, int DS, bool RRM = false>
 __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const double (&w)[E], double (&l)[E],
                                       double (&th)[MoTheta<MODE, DS>::N], bool given, int &parity, int &sweeps) {
     constexpr int NTRI = DS * (DS + 1) / 2;
@@ -196,11 +210,13 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
                 l[j] = q < n ? r : 0.0;
                 swr = __builtin_fma(w[j], l[j], swr);
             }
-            sl_block_sum2<MO_KMAX>(swr, none, sh.slots, parity);
-            const double sigma2 = swr / s0;
-            if (!(sigma2 > 0.0 && sigma2 < __builtin_inf())) return 1;
+            if (!RRM) {
+                sl_block_sum2<MO_KMAX>(swr, none, sh.slots, parity);
+                const double sigma2 = swr / s0;
+                if (!(sigma2 > 0.0 && sigma2 < __builtin_inf())) return 1;
 #pragma unroll
-            for (int j = 0; j < E; ++j) l[j] = 0.5 * l[j] / sigma2;
+                for (int j = 0; j < E; ++j) l[j] = 0.5 * l[j] / sigma2;
+            }
 #pragma unroll
             for (int c = 0; c < DS; ++c) th[c] = m[c];
             return 0;
@@ -303,7 +319,13 @@ __device__ __forceinline__ int mo_fit(const MoShared &sh, int n, int d, const do
                 ss = __builtin_fma(x[c], x[c], ss);
                 p = __builtin_fma(x[c], th[c], p);
             }
-            l[j] = q < n ? ss - p * p : 0.0;
+            if (RRM) {
+                double pp = p * p;
+                sl_keep(pp);
+                l[j] = q < n ? ss - pp : 0.0;
+            } else {
+                l[j] = q < n ? ss - p * p : 0.0;
+            }
         }
     }
     return rc;
@@ -389,6 +411,121 @@ __device__ __forceinline__ int mo_estep_constrained(const double (&l)[E], double
     return rc;
 }
 
+// rrm.update_weights (rrm.py:12-33) on this thread's samples.  The reference minimises g(alpha) = alpha (log sum_i
+// exp(-l_i / alpha) - log((1 - eps) n)) over alpha = exp(xi) by scipy's Brent search and returns w_i = exp(-l_i / alpha)
+// / sum_j exp(-l_j / alpha).  g is convex and stationary where the entropy of w equals log((1 - eps) n):
+//     H(xi) = log S + (sum phi_i t_i) / S = log((1 - eps) n),  t_i = (l_i - min l) / alpha, phi_i = exp(-t_i), S = sum phi_i
+// (the shift by min l moves g by a constant, leaves w as it is and makes every form overflow-safe: a covariance's
+// losses are negative whenever log det is; S >= 1, so the reference's floor of 1e-16 under every phi is not needed and
+// is DROPPED -- DESIGN 3.4f).  H increases in xi from log m, m the samples tied at the minimum, to log n, and dH/dxi =
+// Var_w(t): the CONTRACT is that root, not Brent's iterate.  From xi = log mean(l - min l) a bracket is grown
+// geometrically (steps 1, 2, 4, ...), then Newton steps, bisection where a step leaves the bracket or shrinks it too
+// slowly; stops when the bracket is one ulp wide, the step is below one ulp or |H - target| <= 16 eps (1 + target): log
+// S and the mean of t, each at most 1 + target here, carry the rounding of a sum of E + 8 terms per lane and wave.
+// Each evaluation is the samples' arithmetic (one exp each) + ONE block sum of {S, sum phi t, sum phi t^2}.
+// m >= (1 - eps) n, or no sign change down to MO_XI_MIN: there is no root, the minimiser runs off to alpha -> 0 and
+// the rule returns that limit, 1 / m on the minima and 0 elsewhere (had_root false; all-equal losses are m = n).
+// Returns 0, 1 (a loss that is not finite: w untouched) or 2 (MO_ROOT_CAP evaluations).  All threads call.
+template <int E>
+__device__ __forceinline__ int mo_estep_rrm(const double (&l)[E], double (&w)[E], int n, double eps,
+                                            const MoShared &sh, int &parity, int &evals, bool &had_root) {
+    const int tid = threadIdx.x;
+    evals = 0;
+    had_root = false;
+    double lmin = __builtin_inf(), none = -__builtin_inf();
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const bool v = tid + j * SL_THREADS < n;
+        lmin = (v && l[j] < lmin) ? l[j] : lmin;
+    }
+    sl_block_minmax<MO_KMAX>(lmin, none, sh.slots, parity);
+    double l0[E], phi[E], c[3] = {0.0, 0.0, 0.0};                  // c: ties at the minimum, sum l0, losses not finite
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const bool v = tid + j * SL_THREADS < n;
+        const double dl = l[j] - lmin;
+        l0[j] = v ? dl : 0.0;
+        phi[j] = (v && dl == 0.0) ? 1.0 : 0.0;
+        c[0] += phi[j];
+        c[1] += l0[j];
+        c[2] += (v && !(fabs(dl) < __builtin_inf())) ? 1.0 : 0.0;
+    }
+    sl_block_sum<3, MO_KMAX>(c, sh.slots, parity);
+    if (c[2] != 0.0) return 1;
+    const double keep = (1.0 - eps) * (double)n, target = log(keep), m = c[0];
+    bool root = m < keep;
+    double S = m;
+    int rc = 0;
+    if (root) {
+        double s = log(c[1] / (double)n);
+        s = (s > MO_XI_MIN) ? s : MO_XI_MIN;
+        s = (s < MO_XI_MAX) ? s : MO_XI_MAX;
+        const double gtol = 16.0 * MO_EPS * (1.0 + target);
+        double lo = MO_XI_MIN, hi = MO_XI_MAX, grow = 1.0, dxold = 0.0, dx = 0.0;
+        bool has_lo = false, has_hi = false;
+        for (;;) {
+            const double inva = exp(-s);
+            double a[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const bool v = tid + j * SL_THREADS < n;
+                double t = l0[j] * inva;
+                t = (t < MO_TMAX) ? t : MO_TMAX;
+                const double p = v ? exp(-t) : 0.0;
+                phi[j] = p;
+                a[0] += p;
+                a[1] = __builtin_fma(p, t, a[1]);
+                a[2] = __builtin_fma(p * t, t, a[2]);
+            }
+            sl_block_sum<3, MO_KMAX>(a, sh.slots, parity);
+            ++evals;
+            S = a[0];
+            const double mt = a[1] / S;
+            const double f = log(S) + mt - target, fp = a[2] / S - mt * mt;
+            if (fabs(f) <= gtol) break;
+            const bool bracketed = has_lo && has_hi;
+            if (f < 0.0) { lo = s; has_lo = true; } else { hi = s; has_hi = true; }
+            if (evals >= MO_ROOT_CAP) { rc = 2; break; }
+            double sn;
+            if (!(has_lo && has_hi)) {
+                if (f < 0.0) {
+                    if (s >= MO_XI_MAX) break;                      // (losses of 1e300: the widest alpha is the answer)
+                    sn = s + grow;
+                    sn = (sn < MO_XI_MAX) ? sn : MO_XI_MAX;
+                } else {
+                    if (s <= MO_XI_MIN) { root = false; break; }    // the bracket's lower end is above the target
+                    sn = s - grow;
+                    sn = (sn > MO_XI_MIN) ? sn : MO_XI_MIN;
+                }
+                grow *= 2.0;
+            } else {
+                if (!bracketed) { dxold = hi - lo; dx = dxold; }
+                sn = s - f / fp;
+                if (fp > 0.0 && sn == s) break;                     // the Newton step is below one ulp of xi
+                if (!(fp > 0.0) || !(sn > lo && sn < hi) || fabs(2.0 * f) > fabs(dxold * fp)) {
+                    dxold = dx;
+                    dx = 0.5 * (hi - lo);
+                    sn = lo + dx;
+                } else {
+                    dxold = dx;
+                    dx = fabs(sn - s);
+                }
+                if (sn == lo || sn == hi) break;                    // the bracket is one ulp wide
+            }
+            s = sn;
+        }
+    }
+    if (!root) {
+        S = m;
+#pragma unroll
+        for (int j = 0; j < E; ++j) phi[j] = (tid + j * SL_THREADS < n && l0[j] == 0.0) ? 1.0 : 0.0;
+    }
+    had_root = root;
+#pragma unroll
+    for (int j = 0; j < E; ++j) w[j] = phi[j] / S;                  // rrm.py:27-32 (every exit left phi and S at one xi)
+    return rc;
+}
+
 // the kernels' LDS in doubles: the sample (an even count), then the slots
 __host__ __device__ constexpr size_t mo_slots_off(int64_t nd) { return (size_t)((nd + 1) & ~(int64_t)1); }
 __device__ __forceinline__ void mo_carve(MoShared &sh, double *sm, int nd) {
@@ -399,6 +536,11 @@ static size_t mo_lds_bytes(int64_t nd) { return (mo_slots_off(nd) + sl_slot_doub
 
 // MODE 0 / 1 / 2: mean / pca / covariance.  theta_out: [d], [d], [d * d]; info: { outer iterations, inner iterations of
 // the last E-step, inner iterations in all | Jacobi sweeps in all | E-steps with the constraint active, flag }.
+// MODE 3 / 4 / 5: the same three fits under RRM (rrm.py:36-52, :94-124) -- new MODE values and not a further template
+// parameter, so that the RLVI instantiations keep their symbols and their instructions: first weights 1 / n, the weight
+// rule mo_estep_rrm with eps in the place of n_eff, the fits' RRM forms (mo_fit); info: { outer iterations, evaluations of the
+// last root-find, evaluations in all | Jacobi sweeps in all | evaluations in all, flag }; flag 1 as well for eps outside
+// (0, 1), (1 - eps) n <= 1 and a loss that is not finite.
 // BATCH: workgroup b works on problem b of a contiguous batch (X [B, n, d], theta [B, d] or [B, d * d], weights [B, n],
 // info [B, 4]; theta_init and n_eff are the whole batch's) behind wave-uniform pointer offsets -- a template flag, as
 // in linreg_rlvi_kernel: the single form keeps its instructions.  `status` is the ONE word of the workspace for all
@@ -410,11 +552,13 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
     double etol, int emaxiter, double n_eff, double *__restrict__ theta_out, double *__restrict__ w_out,
     int32_t *__restrict__ info, int32_t *__restrict__ status) {
     extern __shared__ double sm[];
-    constexpr int NT = MoTheta<MODE, DS>::N;
+    constexpr int FIT = MODE % 3;                      // which of the three fits
+    constexpr bool RRM = MODE >= 3;
+    constexpr int NT = MoTheta<FIT, DS>::N;
     if constexpr (BATCH) {
         const size_t b = blockIdx.x;                   // (64-bit offsets: B n d passes 2^31)
         X += b * (size_t)n * (size_t)d;
-        theta_out += b * (size_t)(MODE == 2 ? d * d : d);
+        theta_out += b * (size_t)(FIT == 2 ? d * d : d);
         w_out += b * (size_t)n;
         info += b * 4;
     }
@@ -430,7 +574,7 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
         sm[q] = v;
         if (!(fabs(v) < __builtin_inf())) nbad += 1.0;
     }
-    const bool given = MODE == 1 && theta_init != nullptr;
+    const bool given = FIT == 1 && theta_init != nullptr;
     double th[NT], prev[NT];
 #pragma unroll
     for (int k = 0; k < NT; ++k) { th[k] = 0.0; prev[k] = 0.0; }
@@ -444,25 +588,33 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
         }
     }
     if (MODE == 2 && !(n_eff > 0.0 && n_eff < (double)n)) nbad += 1.0;
+    if (RRM && !(n_eff > 0.0 && n_eff < 1.0 && (1.0 - n_eff) * (double)n > 1.0)) nbad += 1.0;    // (n_eff: eps)
     sl_block_sum2<MO_KMAX>(nbad, none, sh.slots, parity);                    // (its barrier publishes the sample)
     bool ok = nbad == 0.0;
 
     double w[E], l[E];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-        w[j] = (tid + j * SL_THREADS < n) ? 1.0 : 0.0;              // rlvi.py:47 / :112 / :132
+        // rlvi.py:47 / :112 / :132; rrm.py:37 / :95 / :111
+        w[j] = (tid + j * SL_THREADS < n) ? (RRM ? 1.0 / (double)n : 1.0) : 0.0;
         l[j] = 0.0;
     }
     int outer = 0, inner_last = 0, count = 0;
     bool capped = false;
     if (ok) {
-        const int rc = mo_fit<MODE, E, DS>(sh, n, d, w, l, th, given, parity, count);
+        const int rc = mo_fit<FIT, E, DS, RRM>(sh, n, d, w, l, th, given, parity, count);
         ok = rc != 1;
         capped = rc == 2;
     }
     while (ok && outer < maxiter) {
         ++outer;
-        if (MODE == 2) {
+        if (RRM) {
+            bool had_root;
+            const int rc = mo_estep_rrm<E>(l, w, n, n_eff, sh, parity, inner_last, had_root);
+            if (rc == 1) { ok = false; break; }
+            capped = capped || rc == 2;
+            if (FIT != 1) count += inner_last;
+        } else if (MODE == 2) {
             bool active;
             int evals;
             const int rc = mo_estep_constrained<E>(l, w, n, n_eff, etol, emaxiter, sh, parity, inner_last, active,
@@ -482,12 +634,12 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
         }
 #pragma unroll
         for (int k = 0; k < NT; ++k) prev[k] = th[k];
-        const int rc = mo_fit<MODE, E, DS>(sh, n, d, w, l, th, false, parity, count);
+        const int rc = mo_fit<FIT, E, DS, RRM>(sh, n, d, w, l, th, false, parity, count);
         if (rc == 1) { ok = false; break; }
         capped = capped || rc == 2;
         // ||theta - prev|| / ||prev|| <= tol (the Frobenius norms of the full matrix for the covariance)
         double dn = 0.0, pn = 0.0;
-        if (MODE == 2) {
+        if (FIT == 2) {
 #pragma unroll
             for (int i = 0; i < DS; ++i) {
 #pragma unroll
@@ -509,7 +661,7 @@ __global__ __launch_bounds__(SL_THREADS) void moments_rlvi_kernel(
     }
     if (ok) {
         if (tid == 0) {
-            if (MODE == 2) {
+            if (FIT == 2) {
 #pragma unroll
                 for (int i = 0; i < DS; ++i) {
 #pragma unroll
@@ -585,12 +737,52 @@ __global__ __launch_bounds__(SL_THREADS) void moments_uwc_kernel(const double *_
     }
 }
 
+// rrm.update_weights on its own: info = { root-find evaluations, 0, 1 if there was a root (0: the alpha -> 0 limit),
+// flag }
+template <int E>
+__global__ __launch_bounds__(SL_THREADS) void moments_rrm_weights_kernel(const double *__restrict__ losses, int n,
+                                                                         double eps, double *__restrict__ out,
+                                                                         int32_t *__restrict__ info,
+                                                                         int32_t *__restrict__ status) {
+    extern __shared__ double sm[];
+    MoShared sh;
+    mo_carve(sh, sm, 0);
+    const int tid = threadIdx.x;
+    int parity = 0;
+    double l[E], w[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const int q = tid + j * SL_THREADS;
+        l[j] = losses[q < n ? q : 0];
+        w[j] = 0.0;
+    }
+    // (every thread sees the same eps and n; a loss that is not finite is mo_estep_rrm's to report)
+    const bool args = eps > 0.0 && eps < 1.0 && (1.0 - eps) * (double)n > 1.0;
+    int evals = 0, rc = 1;
+    bool had_root = false;
+    if (args) rc = mo_estep_rrm<E>(l, w, n, eps, sh, parity, evals, had_root);
+    if (rc != 1) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const int q = tid + j * SL_THREADS;
+            if (q < n) out[q] = w[j];
+        }
+    }
+    if (tid == 0) {
+        info[0] = evals;
+        info[1] = 0;
+        info[2] = had_root ? 1 : 0;
+        info[3] = rc;
+        if (rc == 2) atomicOr(status, RLVI_ST_NOCONV);
+    }
+}
+
 static int mo_check(int64_t n, int64_t d) {
     if (n <= 0 || d <= 0) return RLVI_E_SHAPE;
     return (n >= 2 && n <= SL_MAXN && d <= MO_MAXD && n * d <= MO_MAXND) ? 0 : RLVI_E_LIMIT;
 }
 
-// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms
+// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms (MODE 3 .. 5: n_eff is eps)
 template <int MODE, bool BATCH = false>
 static int mo_launch(const double *X, const double *theta_init, int64_t n, int64_t d, int maxiter, double tol,
                      double etol, int emaxiter, double n_eff, double *theta, double *w_out, int32_t *info, void *ws,
@@ -695,4 +887,68 @@ extern "C" int rlvi_update_weights_constrained_f64(const double *losses, int64_t
     if (n <= SL_THREADS) return go(moments_uwc_kernel<1>);
     if (n <= 4 * SL_THREADS) return go(moments_uwc_kernel<4>);
     return go(moments_uwc_kernel<16>);
+}
+
+// ---- Robust Risk Minimization: estep_tol / estep_maxiter have no counterpart (the rule is a root, not a fixed point)
+extern "C" int rlvi_rrm_mean_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
+                                 double *theta, double *weights, int32_t *info, void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws)) return e;
+    return mo_launch<3>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_rrm_pca_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
+                                const double *theta_init, double *theta, double *weights, int32_t *info, void *ws,
+                                void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, theta_init, theta, weights, info, ws)) return e;
+    return mo_launch<4>(sample, theta_init, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_rrm_covariance_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
+                                       double *theta, double *weights, int32_t *info, void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws)) return e;
+    return mo_launch<5>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rlvi_rrm_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
+                                       int maxiter, double tol, double *theta, double *weights, int32_t *info,
+                                       void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws, batch)) return e;
+    return mo_launch<3, true>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                              static_cast<hipStream_t>(stream), batch);
+}
+
+extern "C" int rlvi_rrm_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
+                                      int maxiter, double tol, const double *theta_init, double *theta,
+                                      double *weights, int32_t *info, void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, theta_init, theta, weights, info, ws, batch)) return e;
+    return mo_launch<4, true>(sample, theta_init, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                              static_cast<hipStream_t>(stream), batch);
+}
+
+extern "C" int rlvi_rrm_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
+                                             int maxiter, double tol, double *theta, double *weights, int32_t *info,
+                                             void *ws, void *stream) {
+    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws, batch)) return e;
+    return mo_launch<5, true>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                              static_cast<hipStream_t>(stream), batch);
+}
+
+extern "C" int rlvi_rrm_update_weights_f64(const double *losses, int64_t n, double eps, double *out, int32_t *info,
+                                           void *ws, void *stream) {
+    if (sl_any_null({losses, out, info, ws})) return RLVI_E_NULL;
+    if (n <= 0) return RLVI_E_SHAPE;
+    if (n > SL_MAXN) return RLVI_E_LIMIT;
+    if (sl_misaligned({losses, out}, info, ws)) return RLVI_E_ALIGN;
+    int32_t *status = &static_cast<WsHeader *>(ws)->status;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = mo_lds_bytes(0);
+    auto go = [&](auto kern) {
+        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, losses, (int)n, eps, out, info, status);
+    };
+    if (n <= SL_THREADS) return go(moments_rrm_weights_kernel<1>);
+    if (n <= 4 * SL_THREADS) return go(moments_rrm_weights_kernel<4>);
+    return go(moments_rrm_weights_kernel<16>);
 }

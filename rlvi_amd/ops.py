@@ -773,6 +773,87 @@ def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, i
                        ((out, losses.shape[0]),), info, ws)
 
 
+# ---- Robust Risk Minimization (standard-learning/rrm.py): the same kernels with the RRM weight rule; eps where the
+# entries above take n_eff, info = {outer, evaluations of the last root-find, evaluations | Jacobi sweeps in all, flag}.
+def _theta_init(theta_init, d):
+    if theta_init is not None:
+        _require_gpu(theta_init)
+        if not _fp64(theta_init, numel=d):
+            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
+    return _ptr(theta_init)
+
+
+def rrm_mean(sample, eps, maxiter=100, tol=1e-3, theta=None, weights=None, info=None, ws=None):
+    """mean(sample, eps, maxiter, tol) of standard-learning/rrm.py:36-52 as ONE launch on device tensors
+    (rlvi_rrm_mean_f64; no host synchronisation here).  Returns (theta [d], weights [n], info int32[4]); flag 1:
+    nothing was written (data or a loss not finite, eps outside (0, 1), (1 - eps) n <= 1); flag 2: a root-find hit its
+    200 evaluations (RLVI_ST_NOCONV in ws)."""
+    n, d = _sample_shape(sample)
+    return _one_launch("rlvi_rrm_mean_f64", (sample,), (float(eps), int(maxiter), float(tol)),
+                       ((theta, d), (weights, n)), info, ws)
+
+
+def rrm_pca(sample, eps, maxiter=100, tol=1e-2, theta_init=None, theta=None, weights=None, info=None, ws=None):
+    """pca(sample, eps, maxiter, tol, theta_init) of standard-learning/rrm.py:94-107 as ONE launch on device tensors
+    (rlvi_rrm_pca_f64); theta_init as for robust_pca.  Returns (theta [d], weights [n], info); info[2]: Jacobi sweeps
+    in all."""
+    n, d = _sample_shape(sample)
+    return _one_launch("rlvi_rrm_pca_f64", (sample,),
+                       (float(eps), int(maxiter), float(tol), _theta_init(theta_init, d)),
+                       ((theta, d), (weights, n)), info, ws)
+
+
+def rrm_covariance(sample, eps, maxiter=100, tol=1e-2, theta=None, weights=None, info=None, ws=None):
+    """covariance(sample, eps, maxiter, tol) of standard-learning/rrm.py:110-124 as ONE launch on device tensors
+    (rlvi_rrm_covariance_f64).  Returns (theta [d, d], weights [n], info); flag 1 as for rrm_mean, and a pivot that
+    is not safely positive."""
+    n, d = _sample_shape(sample)
+    theta, weights, info = _one_launch(
+        "rlvi_rrm_covariance_f64", (sample,), (float(eps), int(maxiter), float(tol)),
+        ((None if theta is None else theta.view(-1), d * d), (weights, n)), info, ws)
+    return theta.view(d, d), weights, info
+
+
+def rrm_mean_batch(sample, eps, maxiter=100, tol=1e-3, theta=None, weights=None, info=None, ws=None):
+    """B calls of rrm_mean (the rrm.mean of main.py:180-188) as ONE launch (rlvi_rrm_mean_batch_f64): sample
+    [B, n, d], one eps for all -> (theta [B, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    theta, weights, info = _one_launch("rlvi_rrm_mean_batch_f64", (sample,), (float(eps), int(maxiter), float(tol)),
+                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def rrm_pca_batch(sample, eps, maxiter=100, tol=1e-2, theta_init=None, theta=None, weights=None, info=None, ws=None):
+    """B calls of rrm_pca (main.py:489-494) as ONE launch (rlvi_rrm_pca_batch_f64): sample [B, n, d], one eps and one
+    theta_init [d] (or None) for all -> (theta [B, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    theta, weights, info = _one_launch(
+        "rlvi_rrm_pca_batch_f64", (sample,), (float(eps), int(maxiter), float(tol), _theta_init(theta_init, d)),
+        _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def rrm_covariance_batch(sample, eps, maxiter=100, tol=1e-2, theta=None, weights=None, info=None, ws=None):
+    """B calls of rrm_covariance (main.py:539-544) as ONE launch (rlvi_rrm_covariance_batch_f64): sample [B, n, d],
+    one eps for all -> (theta [B, d, d], weights [B, n], info int32[B, 4])."""
+    B, n, d = _batch_shape("sample", sample)
+    theta, weights, info = _one_launch(
+        "rlvi_rrm_covariance_batch_f64", (sample,), (float(eps), int(maxiter), float(tol)),
+        _batch_outs(B, (theta, d * d), (weights, n)), info, ws)
+    return theta.view(B, d, d), weights.view(B, n), info.view(B, 4)
+
+
+def rrm_update_weights(losses, eps, out=None, info=None, ws=None):
+    """update_weights(losses, eps) of standard-learning/rrm.py:12-33 as ONE launch on a device tensor of n <= 4096
+    losses (rlvi_rrm_update_weights_f64): exp(-l / alpha) / sum exp(-l / alpha) at the alpha where their entropy is
+    log((1 - eps) n) -- the exact root of what the reference minimises by Brent's search; with no root, 1 / m on the m
+    minima.  Returns (weights [n], info int32[4] = {evaluations, 0, 1 if there was a root, flag})."""
+    _require_gpu(losses)
+    if not _fp64(losses, dims=1):
+        raise ValueError("losses [n] must be a contiguous fp64 device tensor")
+    return _one_launch("rlvi_rrm_update_weights_f64", (losses,), (float(eps),), ((out, losses.shape[0]),), info, ws)
+
+
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,
                          iters=None):
     """One mini-batch of online-learning/main.py:293-297 in ONE launch on device tensors: residuals =

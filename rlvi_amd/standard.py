@@ -282,10 +282,15 @@ def _gauss_losses(sample, theta, w):
     return 0.5 * r / (w @ r / np.sum(w))
 
 
-def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None):
+def _rrm_eps(what, eps, n):
+    if not (0.0 < eps < 1.0 and (1.0 - eps) * n > 1.0):
+        raise ValueError(f"{what} needs 0 < eps < 1 and (1 - eps) n > 1: got eps = {eps}, n = {n}")
+
+
+def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None, rrm=False):
     """one_launch=True of mean / pca / covariance: one pinned H2D copy of the sample (and theta_init), ONE launch
     (rlvi_robust_mean_f64 / _pca_f64 / _covariance_f64), one pinned D2H copy of {theta, weights, info}, one host
-    wait."""
+    wait.  rrm: the estimators of rlvi_amd/rrm.py on the same path (rlvi_rrm_mean_f64 / _pca_f64 / _covariance_f64)."""
     xh = np.ascontiguousarray(sample, dtype=np.float64)
     if xh.ndim != 2:
         raise ValueError("sample must be [n, d]")
@@ -296,9 +301,14 @@ def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None
     # before anything reaches the device
     if not np.isfinite(xh).all() or (init is not None and not np.isfinite(init).all()):
         raise ValueError("Input contains NaN or infinity.")
-    if kind == "covariance" and not 0.0 < eps < 1.0:
+    if rrm:
+        _rrm_eps(f"rrm.{kind}", eps, n)
+    elif kind == "covariance" and not 0.0 < eps < 1.0:
         raise ValueError(f"covariance(one_launch=True) needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
     if n == 0 or d == 0 or not ops.moments_check(n, d):
+        if rrm:
+            raise _lib.RlviError(f"rrm.{kind} takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with n d <= 16384 "
+                                 f"in its one launch: got n = {n}, d = {d}")
         raise _lib.RlviError(f"{kind}(one_launch=True) takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with "
                              f"n d <= 16384 in its one launch: got n = {n}, d = {d} (one_launch=False has no such "
                              f"limit)")
@@ -308,13 +318,17 @@ def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None
 
     def launch(v, out):
         x_dev = v[0].view(n, d)
-        if kind == "mean":
+        if rrm:
+            init_kw = dict(theta_init=None if init is None else v[1]) if kind == "pca" else {}
+            getattr(ops, "rrm_" + kind)(x_dev, eps, maxiter=maxiter, tol=tol, ws=ws, **init_kw, **out)
+        elif kind == "mean":
             ops.robust_mean(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
         elif kind == "pca":
             ops.robust_pca(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws, **out)
         else:
             ops.robust_covariance(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
-    theta, w, inf, _ = _one_launch_roundtrip(dev, "moments_" + kind, [(xh, n * d), (init, d)], nt, n, launch)
+    theta, w, inf, _ = _one_launch_roundtrip(dev, ("rrm_" if rrm else "moments_") + kind, [(xh, n * d), (init, d)], nt,
+                                             n, launch)
     inf = inf.copy()
     if inf[3] == 1:
         if kind == "covariance":
@@ -322,7 +336,7 @@ def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None
         raise ValueError(f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely "
                          f"positive")
     if inf[3] == 2:
-        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
+        ws.raise_on_status(("rrm." if rrm else "") + kind, mask=_lib.ST_NOCONV)
     theta = theta.copy().reshape((d, d) if kind == "covariance" else (d,))
     if return_info:
         return theta, w.copy(), inf
@@ -538,35 +552,42 @@ def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, return_info=False):
     return _batch_results(theta, w, inf, B, (d + 1,), n, return_info)
 
 
-def _moments_batch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None):
+def _moments_batch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None, rrm=False):
+    """mean_batch / pca_batch / covariance_batch; rrm: those of rlvi_amd/rrm.py (rlvi_rrm_*_batch_f64)"""
     xh, _, B, n, d = _batch_inputs("sample", sample)
     init = None if theta_init is None else np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
     if init is not None and init.shape[0] != d:
         raise ValueError("theta_init must have the samples' d elements")
     if init is not None and not np.isfinite(init).all():
         raise ValueError("Input contains NaN or infinity.")
-    if kind == "covariance" and not 0.0 < eps < 1.0:
+    if rrm:
+        _rrm_eps(f"rrm.{kind}_batch", eps, n)
+    elif kind == "covariance" and not 0.0 < eps < 1.0:
         raise ValueError(f"covariance_batch needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
     if n == 0 or d == 0 or not ops.moments_check(n, d):
-        raise _lib.RlviError(f"{kind}_batch takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with n d <= 16384 "
-                             f"in its one launch: got n = {n}, d = {d}")
+        raise _lib.RlviError(f"{'rrm.' if rrm else ''}{kind}_batch takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions "
+                             f"with n d <= 16384 in its one launch: got n = {n}, d = {d}")
     dev = _dev()
     ws = ops.workspace(dev, n, 0)
     shape = (d, d) if kind == "covariance" else (d,)
 
     def launch(v, out):
         x_dev = v[0].view(B, n, d)
-        if kind == "mean":
+        if rrm:
+            init_kw = dict(theta_init=None if init is None else v[1]) if kind == "pca" else {}
+            getattr(ops, f"rrm_{kind}_batch")(x_dev, eps, maxiter=maxiter, tol=tol, ws=ws, **init_kw, **out)
+        elif kind == "mean":
             ops.robust_mean_batch(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
         elif kind == "pca":
             ops.robust_pca_batch(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws,
                                  **out)
         else:
             ops.robust_covariance_batch(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
-    theta, w, inf, _ = _one_launch_roundtrip(dev, "moments_batch_" + kind, [(xh, B * n * d), (init, d)],
+    theta, w, inf, _ = _one_launch_roundtrip(dev, ("rrm_batch_" if rrm else "moments_batch_") + kind,
+                                             [(xh, B * n * d), (init, d)],
                                              int(np.prod(shape)), n, launch, batch=B)
     inf = inf.copy().reshape(B, 4)
-    _batch_flags(kind + "_batch", ws, inf, return_info,
+    _batch_flags(("rrm." if rrm else "") + kind + "_batch", ws, inf, return_info,
                  "Singular covariance matrix" if kind == "covariance" else
                  f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely positive")
     return _batch_results(theta, w, inf, B, shape, n, return_info)
