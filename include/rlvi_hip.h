@@ -98,6 +98,10 @@ int rlvi_workspace_set_option(void *ws, const char *name, int value);
  * 2 wave tiles in four-wave workgroups, 3 wave tiles in 16-wave workgroups, 4 word-wise bf16 / fp16 wave tiles (odd row
  * lengths), 5 long rows (more than 512 vectors per row: a wave or a workgroup per row, three passes); + 16 with a timed hold. */
 int rlvi_workspace_last_mstep_form(const void *ws);
+/* The kernel instantiation behind that form (host side, tests of the dispatch): V | G << 8 | KMAX << 16 -- elements per
+ * vector access, lanes per row, vector slots per lane.  G = KMAX = 0 for the long-row form and for the word-wise
+ * tile (whose V is 1: single 2-byte elements); 0 for a workspace that has seen no M-step launch. */
+int rlvi_workspace_last_mstep_shape(const void *ws);
 /* Forget the guesses earlier calls left for the next one (E-step trajectory and minimum, threshold key). */
 int rlvi_workspace_reset_warm(void *ws, void *stream);
 /* Byte offset (and size through *bytes) of a region of the workspace layout, for tools and tests: "records"
@@ -122,6 +126,10 @@ size_t rlvi_workspace_region(const char *name, size_t *bytes);
  * Any C up to 2^20 (RLVI_E_LIMIT beyond); rows of more than 512 vectors (C > 2048 fp32 / 4096 bf16 with aligned
  * rows, C > 512 with an odd length or pitch) take a form that reads the row three times (a wave per row, a workgroup
  * per row for batches of up to four rows per CU).
+ * The vector width V is the widest of {16 / sizeof(element), 4, 2, 1} that divides C, ld, ldg and the element offsets
+ * logits / sizeof(element) and grad_logits / sizeof(element): a dense view whose base is not 16-byte aligned (row 1 of a
+ * batch split along its rows) or an odd pitch runs narrower vectors, and leaves the LDS wave tiles for register rows;
+ * the results are the same to rounding (rlvi_workspace_last_mstep_shape shows V).
  *
  * Evaluation form: weights == NULL (then idx and residuals must be NULL too) computes the plain
  * mean CE and the top-1 percentage of the batch -- utils.evaluate (deep-learning/utils.py:48-62)

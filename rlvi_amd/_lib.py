@@ -32,6 +32,7 @@ SIGNATURES = {
     "rlvi_workspace_set_option": (_int, [_vp, ctypes.c_char_p, _int]),
     "rlvi_workspace_reset_warm": (_int, [_vp, _vp]),
     "rlvi_workspace_last_mstep_form": (_int, [_vp]),
+    "rlvi_workspace_last_mstep_shape": (_int, [_vp]),
     "rlvi_workspace_region": (ctypes.c_size_t, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t)]),
     "rlvi_peer_inbox_bytes": (ctypes.c_size_t, []),
     "rlvi_peer_alloc": (_int, [ctypes.POINTER(ctypes.c_void_p)]),

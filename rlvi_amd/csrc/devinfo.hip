@@ -200,7 +200,7 @@ extern "C" int rlvi_tune_overrides(char *buf, int len) {
 // as opposed to the process-wide tuning knobs above)
 namespace rlvi {
 namespace {
-struct WsOptions { int v[WSOPT_COUNT]; bool set[WSOPT_COUNT]; int last_mstep; };
+struct WsOptions { int v[WSOPT_COUNT]; bool set[WSOPT_COUNT]; int last_mstep, last_shape; };
 std::unordered_map<const void *, WsOptions> g_wsopt;
 std::mutex g_wsopt_mu;
 }  // namespace
@@ -210,9 +210,11 @@ int ws_option(const void *ws, int which, int dflt) {
     auto it = g_wsopt.find(ws);
     return (it != g_wsopt.end() && it->second.set[which]) ? it->second.v[which] : dflt;
 }
-void ws_note_mstep(const void *ws, int code) {
+void ws_note_mstep(const void *ws, int code, int v, int g, int kmax) {
     std::lock_guard<std::mutex> lk(g_wsopt_mu);
-    g_wsopt[ws].last_mstep = code;
+    WsOptions &o = g_wsopt[ws];
+    o.last_mstep = code;
+    o.last_shape = v | g << 8 | kmax << 16;
 }
 void ws_options_forget(const void *ws) {
     std::lock_guard<std::mutex> lk(g_wsopt_mu);
@@ -240,6 +242,15 @@ extern "C" int rlvi_workspace_last_mstep_form(const void *ws) {
     std::lock_guard<std::mutex> lk(rlvi::g_wsopt_mu);
     auto it = rlvi::g_wsopt.find(ws);
     return it == rlvi::g_wsopt.end() ? 0 : it->second.last_mstep;
+}
+
+// The instantiation behind that form: V | G << 8 | KMAX << 16 -- elements per vector, lanes per row, vector slots per
+// lane; G = KMAX = 0 for the long-row and the word-wise forms (V = 1 for the latter: single 2-byte elements); 0 = none
+// yet.
+extern "C" int rlvi_workspace_last_mstep_shape(const void *ws) {
+    std::lock_guard<std::mutex> lk(rlvi::g_wsopt_mu);
+    auto it = rlvi::g_wsopt.find(ws);
+    return it == rlvi::g_wsopt.end() ? 0 : it->second.last_shape;
 }
 
 extern "C" int rlvi_device_cus(void) { return rlvi::device_info().cus; }

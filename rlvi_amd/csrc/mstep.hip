@@ -1006,7 +1006,7 @@ static int launch_mstep(const MstepCall<T> &c) {
         int64_t nb = (B + rows_per_block - 1) / rows_per_block;
         if (nb > MSTEP_MAX_BLOCKS) nb = MSTEP_MAX_BLOCKS;
         if (nb < 1) nb = 1;
-        ws_note_mstep(c.ws, 1);
+        ws_note_mstep(c.ws, 1, V, G, KMAX);
         return c.finish(c.template rows<V, G, KMAX>(0, nb), nb);
     }
     // (extra LDS per workgroup -- fewer resident workgroups per CU, the dispatcher then hands the remaining tiles
@@ -1055,12 +1055,12 @@ static int launch_mstep(const MstepCall<T> &c) {
             // (nb16 workgroups of 16 waves = ONE tile per wave, never a capped grid: the fp32 kernel of this form
             //  relies on it -- 32-bit tile index, one pass through its body, no stride)
             nb = nb16;
-            ws_note_mstep(c.ws, 3);
+            ws_note_mstep(c.ws, 3, V, G, KMAX);
             rc = launch_wave<T, V, G, KMAX, WPB16>(c, exact, nb, nfull, 0, 0);
         }
     }
     if (!cuwide) {
-        ws_note_mstep(c.ws, 2 + (hold_ticks != 0 ? 16 : 0));
+        ws_note_mstep(c.ws, 2 + (hold_ticks != 0 ? 16 : 0), V, G, KMAX);
         rc = launch_wave<T, V, G, KMAX, WPB>(c, exact, nb, nfull, hold_ticks, gen_ticks);
     }
     return c.template tail_and_finish<V, G, KMAX>(rc, nfull * R, nb);
@@ -1134,7 +1134,7 @@ static int dispatch_gk(const MstepCall<T> &c) {
         const bool wide = B <= 4 * (int64_t)c.cus;
         int64_t nb = wide ? B : (B + MSTEP_WAVES - 1) / MSTEP_WAVES;
         if (nb > MSTEP_MAX_BLOCKS) nb = MSTEP_MAX_BLOCKS;
-        ws_note_mstep(c.ws, 5);
+        ws_note_mstep(c.ws, 5, V, 0, 0);
         auto go = [&](auto kern) {
             return launch(kern, dim3((unsigned)nb), dim3(MSTEP_THREADS), 0, c.st, c.logits, c.ld, c.labels, c.idx,
                           B, C, c.N, c.weights, c.residuals, c.inv_scale, c.grad_scale, c.grad, c.ldg, c.part, c.status,
@@ -1171,7 +1171,7 @@ static int launch_bf16w(const MstepCall<T> &c) {
     const int64_t nb = c.tile_grid(nfull, WPB);
     const size_t lds = (size_t)WPB * (4 * 1024 + 64);
     const int kw = ((c.C + 3) / 4 + 1) / 2;        // words of a lane's segment of ceil(C / 4) elements
-    ws_note_mstep(c.ws, 4);
+    ws_note_mstep(c.ws, 4, 1, 0, 0);
     auto go = [&](auto kern) {
         return launch(kern, dim3((unsigned)nb), dim3(WPB * WAVE), lds, c.st, c.logits, c.labels, c.idx, nfull, c.C,
                       c.weights, c.N, c.residuals, c.inv_scale, c.grad_scale, c.grad, c.part, c.status, c.accum,

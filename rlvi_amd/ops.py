@@ -181,6 +181,9 @@ def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_
     fp32, bf16 and fp16 logits run natively; the gradient has the logits' dtype.  grad_scale: an optional
     one-element fp32 device tensor (a GradScaler's scale) that multiplies the gradient only -- read by the kernel
     for fp16 logits, no host sync either way.
+    grad / out: optional buffers of the caller's.  grad must be [B, C] in the dtype the kernel runs the logits in, on
+    their device, with unit column stride (rows may be strided); out four contiguous fp32 elements there: ValueError
+    otherwise, before any launch.  The kernel's vector width follows the alignment of both blocks (include/rlvi_hip.h).
     """
     L = _lib.load()
     _require_gpu(logits, labels, idx, weights, residuals)
@@ -199,10 +202,19 @@ def mstep_fwd_bwd(logits, labels, idx, weights, residuals, inv_scale=None, want_
         out = None
     elif out is None:
         out = torch.empty(4, dtype=torch.float32, device=logits.device)
-    if want_grad and grad is None:
-        grad = torch.empty((B, C), dtype=logits.dtype, device=logits.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.numel() != 4 or not out.is_contiguous()
+          or out.device != logits.device):
+        raise ValueError("out must be four contiguous fp32 elements on the logits' device")
     if not want_grad:
         grad = None
+    elif grad is None:
+        grad = torch.empty((B, C), dtype=logits.dtype, device=logits.device)
+    elif (not torch.is_tensor(grad) or grad.dim() != 2 or grad.shape != (B, C) or grad.dtype != logits.dtype
+          or grad.device != logits.device or grad.stride(1) != 1):
+        # (the C entry writes B rows of C elements of the logits' type at a pitch of grad.stride(0): anything else is
+        #  garbage or a write out of bounds)
+        raise ValueError(f"grad must be a [{B}, {C}] {logits.dtype} tensor on the logits' device with unit column "
+                         "stride (rows may be strided)")
     grad_scale = _check_grad_scale(grad_scale, logits.device)
     ws = ws or workspace(logits.device, N, B)
     rc = _mstep_call(L, logits, labels, idx, weights, residuals, N, B, C,

@@ -97,6 +97,7 @@ def test_workspace_regions_options_and_shape_queries(lib):
     assert lib.rlvi_workspace_set_option(p, b"no_such_option", 1) == -2
     assert lib.rlvi_workspace_set_option(None, b"cold_start", 1) == -1
     assert lib.rlvi_workspace_last_mstep_form(p) == 0
+    assert lib.rlvi_workspace_last_mstep_shape(p) == 0 and lib.rlvi_workspace_last_mstep_shape(None) == 0
     assert lib.rlvi_linear_regression_check(1000, 20) == 0 and lib.rlvi_linear_regression_check(40, 10) == 0
     assert lib.rlvi_linear_regression_check(4096, 31) == 0
     assert lib.rlvi_linear_regression_check(4097, 5) == -5 and lib.rlvi_linear_regression_check(100, 32) == -5
