@@ -43,6 +43,26 @@ __device__ __forceinline__ void write_partial(double *part, double ta, double th
     } else { p[0] = v0; p[1] = v1; p[2] = ta; p[3] = th; }
 }
 
+// write_partial for a caller that is ONE lane (the 16-wave fp32 wave-tile form's thread 0): the same four values, and
+// in accumulate mode the four adds as the hardware instruction itself.  The builtin above goes through the compiler's
+// scheme for a wave-uniform address -- count the active lanes, let the first one add value * count -- which with one
+// lane active multiplies by 1.0 (the same bits) behind four rounds of v_mbcnt / s_bcnt1 / v_cvt / v_mul / branch, all
+// of them between the workgroup's last barrier and the end of the launch.
+__device__ __forceinline__ void write_partial_one_lane(double *part, double ta, double th, float inv_scale,
+                                                       double inv_rows100, int accum) {
+    double *p = part + (size_t)PART_STRIDE * blockIdx.x;
+    const double v0 = ta * (double)inv_scale, v1 = th * inv_rows100;
+    if (accum) {
+        typedef __attribute__((address_space(1))) double gdouble;
+        gdouble *q = (gdouble *)p;
+        const unsigned zero = 0u;
+        asm volatile("global_atomic_add_f64 %0, %1, %2" : : "v"(zero), "v"(v0), "s"(q) : "memory");
+        asm volatile("global_atomic_add_f64 %0, %1, %2 offset:8" : : "v"(zero), "v"(v1), "s"(q) : "memory");
+        asm volatile("global_atomic_add_f64 %0, %1, %2 offset:16" : : "v"(zero), "v"(ta), "s"(q) : "memory");
+        asm volatile("global_atomic_add_f64 %0, %1, %2 offset:24" : : "v"(zero), "v"(th), "s"(q) : "memory");
+    } else { p[0] = v0; p[1] = v1; p[2] = ta; p[3] = th; }
+}
+
 // A row's term of the batch loss.  A weight of exactly zero takes the row out of the sum whatever its NLL: the
 // small-loss baselines and BARE hand their 0/1 selection in as weights, and a row they drop may well have an NLL of
 // +inf (its label's class masked to -inf), which 0 * inf would turn into a NaN loss over the rows they kept.
@@ -453,8 +473,9 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     // Byte offset of this lane's chunk of piece i, 32 bits: the ENTRY_FIRST form's LOADS take a wave-uniform (scalar)
     // base, this offset and an immediate.  With EXACT16 the pieces 0 .. NI-2 are lane * 16 + i * 1024 -- one register,
     // the piece in the immediate as far as the instruction's offset field reaches -- and only the last one is clamped.
-    // (The gradient's stores are as they were: flat stores on 64-bit VGPR addresses -- `grad` passes through the
-    //  empty asm behind the loads, where the compiler loses its address space.)
+    // (The ENTRY_FIRST form's gradient stores take the same offsets on a scalar base of their own: phase C.  `grad`
+    //  passes through the empty asm behind the loads, where the compiler loses its address space, so phase C gives it
+    //  a global pointer again; the other forms' stores are flat ones on 64-bit VGPR addresses.)
     unsigned dma_off[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -484,6 +505,11 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
 
     float acc = 0.0f, hits = 0.0f;
     bool bad = false;
+    // (ENTRY_FIRST: what thread 0 writes the record with.  Thread 0 is in wave 0, and wave 0 of every workgroup has a
+    //  tile -- the launcher's grid is exactly ceil(nfull / 16), launch_wave refuses any other -- so the two arguments
+    //  are taken on the tile path only, behind the loads; a value that both paths needed would be fetched at the entry)
+    int accum_t = 0;
+    double inv_rows100_t = 0.0;
     // Reads first, then writes -- chip-wide, without a word exchanged: when every wave of the launch has ONE
     // tile (a launch of up to 16 waves x CUs tiles: the bench block), a wave does not issue its gradient
     // stores before `hold_ticks` x 10 ns after ITS OWN start, the time the launch's reads need at the
@@ -541,8 +567,14 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
 #endif
         // ENTRY_FIRST: the arguments past the preloaded ones that the body uses pass through here: the compiler asks
         // for them in one burst and waits once, at this point of the program.  (No instruction.)
-        if constexpr (ENTRY_FIRST)
-            asm volatile("" : "+s"(residuals), "+s"(inv_scale), "+s"(grad_scale), "+s"(grad), "+s"(gen_ticks));
+        // (accum and inv_rows100 are the record's, read by thread 0 behind the last barrier: asked for there they are a
+        //  scalar-load round trip at the very end of the launch)
+        if constexpr (ENTRY_FIRST) {
+            asm volatile("" : "+s"(residuals), "+s"(inv_scale), "+s"(grad_scale), "+s"(grad), "+s"(gen_ticks),
+                              "+s"(accum), "+s"(inv_rows100));
+            accum_t = accum;
+            inv_rows100_t = inv_rows100;
+        }
         if (CUWIDE) {
             __builtin_amdgcn_sched_barrier(0);       // (the loads are issued, THEN the barrier)
             __builtin_amdgcn_s_barrier();
@@ -667,19 +699,65 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
                 zf[y] = fmaf(-gscale, pi, zf[y]);
             }
         }
-        if (g_l == 0 && okrow && residuals != nullptr) residuals[ix] = li;
+        if constexpr (ENTRY_FIRST) {
+            // (a global store: a flat one counts in lgkmcnt as well, out of order, and phase C's LDS reads could
+            //  then only be waited for all at once)
+            typedef __attribute__((address_space(1))) float gfloat;
+            if (g_l == 0 && okrow && residuals != nullptr) ((gfloat *)residuals)[ix] = li;
+        } else {
+            if (g_l == 0 && okrow && residuals != nullptr) residuals[ix] = li;
+        }
         acc += okrow ? weighted_nll(li, pi) : 0.0f;
         hits += (hit && okrow) ? 1.0f : 0.0f;
         __builtin_amdgcn_wave_barrier();
         RLVI_STAMP(5);
 
-        // ---- C: flat nontemporal store of the gradient tile
+        // ---- C: nontemporal store of the gradient tile (flat; ENTRY_FIRST: global)
         if (hold_ticks > 0) {
             while (__builtin_amdgcn_s_memrealtime() - t_begin < (unsigned long long)hold_ticks)
                 __builtin_amdgcn_s_sleep(4);
             hold_ticks = gen_ticks > 0 ? hold_ticks + gen_ticks : 0;      // (lab: one hold per generation of tiles)
         }
-        if (grad != nullptr) {
+        if constexpr (ENTRY_FIRST) {
+            // ENTRY_FIRST: the gradient through a GLOBAL pointer (behind the pin `grad` is a generic one, and stores
+            // through it are flat: 64-bit VGPR addresses, and a count in lgkmcnt that comes back out of order), the
+            // tile's base on the scalar unit as the loads' is, and the loads' 32-bit lane offsets.  Global stores leave
+            // lgkmcnt to the LDS reads alone, which return in order: piece i leaves when piece i is back and not when
+            // piece NI-1 is.  The sched_barriers keep the reads, then the stores, in the order of the pieces.
+            if (grad != nullptr) {
+                typedef __attribute__((address_space(1))) char gchar;
+                typedef __attribute__((address_space(1))) vu4 gvu4;
+                gchar *gdst = (gchar *)grad + (uint64_t)((unsigned)t * (unsigned)R) * (unsigned)C * sizeof(T);
+                vu4 st[NI];
+                unsigned gst_off[NI];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    st[i] = tile16[i * WAVE + lane_l];
+                    __builtin_amdgcn_sched_barrier(0);
+                    // (empty: the offset's widening to 64 bits has to happen in THIS block for the instruction
+                    //  selector to see scalar base + 32-bit offset; the loads' widening is in theirs)
+                    // (pieces 1 .. 3 of full pieces: piece 0's register, the piece in the instruction's offset field)
+                    if (EXACT16 && i < NI - 1 && i > 0 && i * 1024 < 4096) continue;
+                    gst_off[i] = dma_off[i];
+                    asm volatile("" : "+v"(gst_off[i]));
+                }
+                // (nontemporal, as before: sc1 and sc1 nt were measured against it and lost)
+#define RLVI_GST(v, o, k) __builtin_nontemporal_store(v, reinterpret_cast<gvu4 *>(gdst + (o) + (k)))
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    if (EXACT16 && i < NI - 1) {
+                        if (i > 0 && i * 1024 < 4096) RLVI_GST(st[i], gst_off[0], i * 1024);
+                        else RLVI_GST(st[i], gst_off[i], 0);
+                    } else if ((i + 1) * WAVE <= nchunk) {
+                        RLVI_GST(st[i], gst_off[i], 0);
+                    } else if (i * WAVE + lane < nchunk) {
+                        RLVI_GST(st[i], gst_off[i], 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#undef RLVI_GST
+            }
+        } else if (grad != nullptr) {
             char *gdst = reinterpret_cast<char *>(grad + row_base * C);
             vu4 st[NI];
 #pragma unroll
@@ -710,16 +788,46 @@ __global__ __launch_bounds__(WPB *WAVE, MSTEP_WAVE_MINW) void mstep_wave_kernel(
     if (ENTRY_FIRST && !has_tile) __syncthreads();
     // every lane of a row's group carried the row's sums: count each row once
     double a = wave_sum((double)(g_l == 0 ? acc : 0.0f));
+    // (hits as an integer butterfly, widened once at the end, was measured for the ENTRY_FIRST form and did not show:
+    //  profiles/r21_mstep_tail.md)
     double h = wave_sum((double)(g_l == 0 ? hits : 0.0f));
     __shared__ double sh[2 * WPB];
     if (lane == 0) { sh[2 * wave] = a; sh[2 * wave + 1] = h; }
     if (bad) atomicOr(status, RLVI_ST_RANGE);
     __syncthreads();
+#ifdef RLVI_MSTEP_STAMPS
+    // stamps 10 and 11: this wave past the workgroup's last barrier; thread 0 with its record's four adds issued
+    unsigned long long *stamps_end = reinterpret_cast<unsigned long long *>(
+        reinterpret_cast<char *>(status) + WS_SCRATCH_OFF) + ((size_t)blockIdx.x * WPB + wave) * 16;
+    if (lane == 0) stamps_end[10] = __builtin_amdgcn_s_memrealtime();
+#endif
     if (threadIdx.x == 0) {
         double ta = 0.0, th = 0.0;
+        if constexpr (ENTRY_FIRST) {
+            // ENTRY_FIRST: the launch ends when the slowest CU's thread 0 is through here.  All sixteen pairs are asked
+            // for before the first add (one LDS round trip, not eight); the sums keep their order, w = 0 .. WPB-1.
+            // (The last pair is asked for behind the first two adds, into registers they have freed: sixteen pairs at
+            //  once are 64 registers, and with the address the kernel would be past 64, a wave per SIMD on paper.)
+            double s[2 * WPB];
 #pragma unroll
-        for (int w = 0; w < WPB; ++w) { ta += sh[2 * w]; th += sh[2 * w + 1]; }
-        write_partial(part, ta, th, inv_scale, inv_rows100, accum);
+            for (int w = 0; w < 2 * WPB - 2; ++w) s[w] = sh[w];
+            __builtin_amdgcn_sched_barrier(0);
+            ta += s[0]; th += s[1];
+            ta += s[2]; th += s[3];
+            __builtin_amdgcn_sched_barrier(0);
+            s[2 * WPB - 2] = sh[2 * WPB - 2]; s[2 * WPB - 1] = sh[2 * WPB - 1];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 2; w < WPB; ++w) { ta += s[2 * w]; th += s[2 * w + 1]; }
+            write_partial_one_lane(part, ta, th, inv_scale, inv_rows100_t, accum_t);
+        } else {
+#pragma unroll
+            for (int w = 0; w < WPB; ++w) { ta += sh[2 * w]; th += sh[2 * w + 1]; }
+            write_partial(part, ta, th, inv_scale, inv_rows100, accum);
+        }
+#ifdef RLVI_MSTEP_STAMPS
+        stamps_end[11] = __builtin_amdgcn_s_memrealtime();
+#endif
     }
 }
 
@@ -971,7 +1079,8 @@ template <typename T, int V, int G, int KMAX, int WPB>
 static int launch_wave(const MstepCall<T> &c, bool exact, int64_t nb, int64_t nfull, int hold_ticks, int gen_ticks) {
     constexpr size_t LDS = (size_t)WPB * ((KMAX * V * sizeof(T) + 15) / 16) * 1024;
     // (the kernel's ENTRY_FIRST form does not stride: a grid that left a wave a second tile would drop it)
-    if (WPB == 16 && sizeof(T) == 4 && nfull > nb * WPB) return RLVI_E_LIMIT;
+    // (nor one with a workgroup that has no tile at all: its thread 0 writes the record from what wave 0's tile path left)
+    if (WPB == 16 && sizeof(T) == 4 && (nfull > nb * WPB || nfull <= (nb - 1) * WPB)) return RLVI_E_LIMIT;
     auto go = [&](auto kern) {
         if constexpr (WPB == 16) {      // (> 64 KiB of dynamic LDS)
             if (const int e = allow_dyn_lds(kern, LDS)) return e;

@@ -2,7 +2,9 @@
 """Phase timeline of the wave-tile M-step kernel from a -DRLVI_MSTEP_STAMPS build.
     RLVI_LIB_PATH=rlvi_amd/librlvi_stamps.so python tools/mstep_stamps.py [--tune NAME=V ...]
 Stamps per wave (first tile): 0 start (the kernel's first instruction), 1 DMA issued, 2 tile landed, 3 row max, 4 row sum,
-5 arithmetic done, 6 stores issued, 7 stores retired.  Prints percentiles in us since the first wave's start."""
+5 arithmetic done, 6 stores issued, 7 stores retired; 10 the wave past the workgroup's last barrier, 11 (thread 0) the
+record's adds issued.  Prints percentiles in us since the first wave's start, and per workgroup of the 16-wave form
+the kernel's end: last store issued / retired, past the barrier, record written."""
 import argparse
 import os
 import sys
@@ -42,6 +44,24 @@ print(f"{len(raw)} waves; us since first wave start (min / p10 / median / p90 / 
 for k, nm in enumerate(names):
     x = (raw[:, k] - t0) / 100.0
     print(f"  {nm:15s} {x.min():6.2f} {np.percentile(x, 10):6.2f} {np.median(x):6.2f} {np.percentile(x, 90):6.2f} {x.max():6.2f}")
+# the kernel's end, per workgroup (16 consecutive waves of the 16-wave form): stamp 10 = a wave past the last barrier,
+# stamp 11 = thread 0 with the record's adds issued (builds from r21 on; zero in older ones)
+if raw[:, 10].max() > 0 and len(raw) % 16 == 0:
+    wg = raw.reshape(-1, 16, 16)
+    last_issue = (wg[:, :, 6].max(axis=1) - t0) / 100.0
+    last_retire = (wg[:, :, 7].max(axis=1) - t0) / 100.0
+    past_bar = (wg[:, :, 10].min(axis=1) - t0) / 100.0
+    rec = (wg[:, 0, 11] - t0) / 100.0
+    for nm, x in (("wg last stores issued", last_issue), ("wg last stores retired", last_retire),
+                  ("wg past final barrier", past_bar), ("wg record adds issued", rec)):
+        print(f"  {nm:22s} {x.min():6.2f} {np.percentile(x, 10):6.2f} {np.median(x):6.2f} {np.percentile(x, 90):6.2f} {x.max():6.2f}")
+    for nm, x in (("last stores issued -> past final barrier", past_bar - last_issue),
+                  ("last stores retired -> past final barrier", past_bar - last_retire),
+                  ("past final barrier -> record adds issued", rec - past_bar)):
+        print(f"  {nm}: median {np.median(x):.2f} p90 {np.percentile(x, 90):.2f} max {x.max():.2f} us")
+    slow = int(np.argmax(rec))
+    print(f"  the launch's last workgroup ({slow}): stores issued {last_issue[slow]:.2f}, retired {last_retire[slow]:.2f}, "
+          f"past barrier {past_bar[slow]:.2f}, record {rec[slow]:.2f}")
 d = np.diff(raw[:, :8], axis=1) / 100.0
 print("phase durations (median / p90): " + ", ".join(f"{names[k+1]} {np.median(d[:, k]):.2f}/{np.percentile(d[:, k], 90):.2f}" for k in range(7)))
 

@@ -17,6 +17,10 @@ rlvi_amd/_build.py and reports per kernel:
   state     E-step only: the slice loads (the first global_load) are issued before ANY scalar load that does not go
             through the argument pointer (the warm-start state) and before the first s_waitcnt lgkmcnt behind one
   vgpr / sgpr / scratch / lds / waves per SIMD
+  phase C   wave-tile M-step only: instructions from the first ds_read_b128 of the gradient tile's way out of LDS to
+            the last gradient store (the *_store_dwordx4 ... nt), and how many flat instructions lie in between
+  behind last barrier   instructions from the last s_barrier to the s_endpgm behind it: the record's tail, which
+            every CU's last wave has on its path
 The stretch is read in layout order, so a side block that the first load's path jumps over is counted too: the
 figures are upper bounds.  Without --all only the two bench instantiations are listed.
 --against DIR: the same for another checkout of the repository (its own sources, its own flags), side by side.
@@ -106,10 +110,29 @@ def analyse(asm):
         clock = next((i for i, (op, _) in enumerate(ins) if op == "s_memrealtime"), None)
         early = next((i for i, (op, _) in enumerate(ins) if op.startswith("s_load") or op == "s_waitcnt"), len(ins))
         stamp_first = clock is not None and clock < early
+        # the kernel's end (wave-tile M-step): phase C from its first LDS read to the last gradient store, and what
+        # runs behind the workgroup's last barrier
+        nt = [i for i, (op, a) in enumerate(ins) if op.endswith("_store_dwordx4") and re.search(r"\bnt\b", a)]
+        phase_c = flat_c = None
+        if nt and "mstep_wave" in name:
+            k = nt[0]
+            # (back to phase B's last LDS write or the hold's loop; the stores of a form that is not EXACT sit in
+            #  branches of their own, so a branch does not end the stretch)
+            while k > 0 and not (ins[k - 1][0].startswith("ds_write") or ins[k - 1][0] in ("s_sleep", "s_barrier")):
+                k -= 1
+            reads = [i for i in range(k, nt[0]) if ins[i][0] == "ds_read_b128"]
+            if reads:
+                phase_c = nt[-1] - reads[0] + 1
+                flat_c = sum(1 for op, _ in ins[reads[0]:nt[-1] + 1] if op.startswith("flat_"))
+        bars = [i for i, (op, _) in enumerate(ins) if op == "s_barrier"]
+        tail = None
+        if bars:
+            end = next((i for i in range(bars[-1], len(ins)) if ins[i][0] == "s_endpgm"), None)
+            tail = None if end is None else end - bars[-1]
         s = sets.get(name, {})
         vg, ag = s.get("num_vgpr", 0), s.get("num_agpr", 0)
         alloc = max((vg + ag + 7) // 8 * 8, 8)
-        rows[name] = dict(preload=preload, instr=first, last=last, burst=burst, waits=waits, rcp=rcp, state=state, stamp_first=stamp_first,
+        rows[name] = dict(phase_c=phase_c, flat_c=flat_c, tail=tail, preload=preload, instr=first, last=last, burst=burst, waits=waits, rcp=rcp, state=state, stamp_first=stamp_first,
                           vgpr=vg + ag,
                           sgpr=int(d.get("next_free_sgpr", s.get("numbered_sgpr", 0))),
                           scratch=s.get("private_seg_size", int(d.get("private_segment_fixed_size", 0))),
@@ -122,8 +145,11 @@ def fmt(r):
     if r is None:
         return "(no such kernel)"
     st = "-" if r["state"] is None else ("yes" if r["state"] else "NO")
+    end = ""
+    if r["phase_c"] is not None:
+        end = f"  phase C {r['phase_c']:3d} ({r['flat_c']} flat)  behind last barrier {r['tail']:3d}"
     return (f"preload {r['preload']:2d}  instr {r['instr']:4d}  last {r['last']:4d} ({r['burst']} loads)  waits {r['waits']}  rcp {'YES' if r['rcp'] else 'no':3s}  "
-            f"state {st:3s}  vgpr {r['vgpr']:3d} sgpr {r['sgpr']:3d} scratch {r['scratch']} lds {r['lds']:5d} waves {r['waves']}")
+            f"state {st:3s}  vgpr {r['vgpr']:3d} sgpr {r['sgpr']:3d} scratch {r['scratch']} lds {r['lds']:5d} waves {r['waves']}" + end)
 
 
 def main():
