@@ -468,7 +468,12 @@ int rlvi_update_weights_online_f64(const double *losses, int64_t n, double tol, 
  * linear_regression (standard-learning/rlvi.py:70-71,:79-80, scipy lstsq on diag(sqrt(w))-scaled
  * rows there): [X | y]^T W [X | y] on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), Cholesky +
  * triangular solves in one workgroup; a rank-deficient design sets RLVI_ST_SINGULAR and gets the
- * minimum-norm solution (Jacobi eigen-decomposition of the Gram matrix), as lstsq gives.  d <= 63. */
+ * minimum-norm solution (Jacobi eigen-decomposition of the Gram matrix), as lstsq gives.  d <= 63.
+ * Rank-deficient means: a column within ~1e-7 (relative) of the span of the columns before it -- the
+ * pivot is compared with the column's own diagonal entry of the Gram matrix, so the SCALE of a column
+ * (1e-60 or 1e9 beside unit columns) never reads as rank deficiency, here and in
+ * rlvi_linear_regression_f64 below.  Accuracy goes as kappa^2 eps, kappa the condition number of
+ * sqrt(W) X with unit-length columns: centre columns that sit far from the origin. */
 int rlvi_wls_solve_f64(const double *X, const double *y, const double *w, int64_t n, int64_t d,
                        double *theta, void *ws, void *stream);
 int rlvi_linreg_losses_f64(const double *X, const double *y, const double *theta,

@@ -198,7 +198,11 @@ __device__ __forceinline__ void sl_gram_collect(const SlSolve &s, int D, sd4_t a
     __syncthreads();
 }
 
-// a pivot of a d x d system whose largest diagonal entry is dmax is "safely positive" above this
+// a pivot of a d x d system is "safely positive" above this fraction of a diagonal entry.  Which entry is the
+// caller's question: the pivot's OWN (linear regression, standard.hip and wls.hip: pivot / own entry is 1 - R^2 of the
+// column on those before it, free of column scale) or the LARGEST (sl_ldlt_solve below, as logistic regression calls
+// it -- its ridge bounds every pivot from below and it raises instead of returning a number -- and the covariance of
+// moments.hip)
 __device__ __forceinline__ double sl_pivot_floor(double dmax, int d) { return dmax * (double)d * 64.0 * SL_EPS; }
 
 // ONE WAVE: G x = rhs by G = L D L^T for the symmetric positive definite G [SL_DP][SL_GPITCH] in LDS, padded with

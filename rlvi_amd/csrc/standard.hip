@@ -198,15 +198,10 @@ __device__ __forceinline__ bool sl_wls(const SlShared &sh, const double *__restr
 #pragma unroll
         for (int c = 0; c < DS; ++c) g[c] = sh.G[t * SL_GPITCH + c];
         double b = t < d ? sh.rhs[t < SL_DP ? t : 0] : 0.0;
-        double dmax = t < d ? sh.G[t * SL_GPITCH + t] : 0.0;
-        dmax = wave_max(dmax);
-        const double piv_min = sl_pivot_floor(dmax, d);
-        bool bad = !(dmax == dmax);
         double dinv = 0.0;                       // lane j: 1 / D_j
 #pragma unroll
         for (int j = 0; j < DS; ++j) {
             const double piv = sl_readlane(g[j], j);
-            bad = bad || (j < d && !(piv > piv_min));
             const double inv = sl_rcp(piv);
             const double l = g[j] * inv;                              // L[t][j] for t > j
             dinv = t == j ? inv : dinv;
@@ -234,6 +229,17 @@ __device__ __forceinline__ bool sl_wls(const SlShared &sh, const double *__restr
 #pragma unroll
         for (int j = DS - 1; j >= 1; --j) b = __builtin_fma(-g[j], sl_readlane(b, j), b);
         if (lane < d) sh.th[lane] = b;
+        // The pivot test, behind the solve: lane t's own pivot against lane t's own diagonal entry, D_t > G_tt d 64 eps.
+        // D_t / G_tt is 1 - R^2 of column t regressed on the columns before it -- it does not move when a column is
+        // rescaled, so a column of 1e-8 or a timestamp of 1e9 beside unit features is not read as rank deficiency
+        // (against the LARGEST diagonal entry it was, and the general path then dropped the column: DESIGN 3.4b).
+        // Lane t still holds 1 / D_t and G is untouched in LDS: the test is floor_t / D_t < 1 with a positive, finite
+        // 1 / D_t (a pivot of 0, inf or NaN leaves a NaN there), nothing of it is live across the factorisation (a
+        // pivot or a floor kept in registers through the loop spills: profiles/r22_linreg_designs.md) and the lanes'
+        // verdicts are combined once -- no broadcast per pivot.
+        const double gtt = t < d ? sh.G[t * SL_GPITCH + t] : 0.0;
+        const double dmax = wave_max(gtt);
+        const bool bad = !(dmax == dmax) || __any(t < d && !(dinv > 0.0 && sl_pivot_floor(gtt, d) * dinv < 1.0));
         if (lane == 0) sh.flag[0] = bad ? 1 : 0;
     }
     __syncthreads();

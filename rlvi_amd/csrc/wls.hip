@@ -5,13 +5,26 @@
 // normal equations  (Xa^T W Xa) with Xa = [X | y]:  the (d+1) x (d+1) weighted Gram matrix is THE
 // dense contraction of this path (n*d^2 flops) and runs on the fp64 matrix cores
 // (v_mfma_f64_16x16x4_f64); a Cholesky factorisation + two triangular solves of the d x d system
-// finish in one workgroup.  A rank-deficient design (a non-positive or negligible Cholesky pivot)
-// sets RLVI_ST_SINGULAR and hands over to wls_minnorm_kernel: the reference's lstsq (LAPACK gelsd)
-// returns the MINIMUM-NORM least-squares solution there, which is pinv(G) X^T W y -- a cyclic Jacobi
-// eigen-decomposition of the d x d Gram matrix in one wave, eigenvalues below d * 64 eps * lambda_max
-// dropped (G carries the design's singular values squared, so exact rank deficiency -- duplicated or
-// empty columns, too few weighted rows -- is what this resolves; sigma_min / sigma_max below ~1e-7 is
-// treated as rank-deficient, where gelsd on the design itself would still resolve it).
+// finish in one workgroup.
+//
+// What counts as rank-deficient.  Pivot j of the factorisation is compared with column j's own diagonal
+// entry: piv_j > G_jj * d * 64 eps.  piv_j / G_jj is 1 - R^2 of column j regressed on the columns before
+// it, so the test does not see the SCALE of any column: a feature of 1e-60 or a timestamp of 1e9 beside
+// unit features is solved to full rank, with the bits (up to the exact power-of-two factor) of the
+// rescaled problem.  It does see collinearity: a column within sqrt(d * 64 eps) ~ 1e-7 of the span of the
+// columns before it is flagged, where gelsd on the design itself would still resolve it.  Short of that
+// the normal equations lose kappa_eq^2 eps, kappa_eq the condition number of sqrt(W) X with every column
+// normalised to unit length (tests/linreg_designs.py: within 32 kappa_eq^2 eps of the exact rational
+// solution).  Columns far from the origin are nearly parallel to each other -- kappa_eq ~ offset / spread
+// -- so a caller with such a design should centre it; no scaling is ever needed.
+//
+// A flagged design sets RLVI_ST_SINGULAR and hands over to wls_minnorm_kernel: the reference's lstsq
+// (LAPACK gelsd) returns the MINIMUM-NORM least-squares solution there, which is pinv(G) X^T W y -- a
+// cyclic Jacobi eigen-decomposition of the d x d Gram matrix in one wave, eigenvalues below d * 64 eps *
+// lambda_max dropped.  That cutoff is on the eigenvalues of G and is NOT free of column scale (neither is
+// the minimum-norm solution itself): it resolves exact rank deficiency -- duplicated or empty columns, too
+// few weighted rows -- of columns of comparable size, and a rank-deficient design that is badly scaled as
+// well loses its small columns there, where gelsd keeps them down to eps * sigma_max.
 //
 // f64 MFMA operand maps (cdna_hip_programming.md section 3): lane l feeds A[i = l&15][k = l>>4] and
 // B[k = l>>4][j = l&15]; the four results of a lane are D[row = (l>>4) + 4*reg][col = l&15].
@@ -110,13 +123,16 @@ __global__ __launch_bounds__(64) void wls_solve_kernel(const double *__restrict_
     }
     __syncthreads();
     // right-looking Cholesky, column j handled by all threads (d <= 63: rows t > j)
+    // The pivot test is on 1 - R^2: pivot j against column j's OWN diagonal entry, taken before the factorisation
+    // touches it (piv_min[j] = G_jj d 64 eps; a NaN or inf entry fails `>`).  Against the largest entry a full-rank
+    // design with one small or one large column read as rank-deficient.
+    __shared__ double piv_min[64];
     bool bad = false;
-    double dmax = 0.0;
-    for (int j = 0; j < d; ++j) dmax = G[j][j] > dmax ? G[j][j] : dmax;
-    const double piv_min = dmax * (double)d * 64.0 * 2.220446049250313e-16;
+    if (t < d) piv_min[t] = G[t][t] * (double)d * 64.0 * 2.220446049250313e-16;
+    __syncthreads();
     for (int j = 0; j < d; ++j) {
         const double piv = G[j][j];
-        if (!(piv > piv_min)) { bad = true; break; }           // uniform: every thread reads G[j][j]
+        if (!(piv > piv_min[j])) { bad = true; break; }        // uniform: every thread reads G[j][j]
         const double dj = sqrt(piv);
         __syncthreads();
         if (t == j) G[j][j] = dj;

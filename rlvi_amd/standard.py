@@ -161,6 +161,11 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, return_info=False):
             dev, "linreg", [(Xh, n * d), (yh, n)], d, n,
             lambda v, out: ops.linear_regression(v[0].view(n, d), v[1], maxiter=maxiter, tol=tol, ws=ws, **out))
         if inf[3] == 0:
+            if not np.isfinite(theta).all():
+                # a NaN or inf in y alone passes the pivot test (which looks at X^T W X) and, with maxiter = 0, no
+                # second solve meets the NaN weights it makes: the reference's error, as the general path below
+                ws.clear_status()
+                raise ValueError("array must not contain infs or NaNs")
             if return_info:
                 return theta.copy(), w.copy(), int(inf[0])
             return theta.copy()
