@@ -660,6 +660,56 @@ int rlvi_rrm_update_weights_f64(const double *losses, int64_t n, double eps, dou
                                 void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The robust linear regressions the reference plots beside RLVI's (standard-learning/main.py:248-357) that are
+ * iterations around a least-squares solve, as ONE launch each (robust_linreg.hip): the workgroup, the weighted
+ * least-squares fit, the limits (n <= 4096, d <= 31), the argument checks and the batch convention of
+ * rlvi_linear_regression_f64 / _batch_f64 above.  X [n, d], y [n] row-major fp64; batch forms: X [B, n, d], y [B, n],
+ * every output with B rows, info int32[B, 4], problem b with exactly the bits of the single entry.
+ *
+ *   rlvi_rrm_linear_regression_f64      standard-learning/rrm.py:55-73: weights = 1 / n, theta = the weighted
+ *               least-squares fit, losses = (y - X theta)^2; then up to `maxiter` times { update_weights(losses, eps)
+ *               -- the exact root of rlvi_rrm_update_weights_f64 --, theta and losses again, stop when ||theta - prev|| /
+ *               ||prev|| <= tol }.  maxiter = 0: the first fit.  theta [d], weights [n].
+ *               info = { outer iterations, evaluations of the last root-find, evaluations in all, flag }.
+ *               flag 1, nothing written: a pivot of a fit's normal equations is not safely positive (the scale-free test
+ *               of rlvi_linear_regression_f64; weights that underflow to exactly 0 can cause it mid-loop) -- the
+ *               reference's lstsq returns the minimum-norm solution there, compose rlvi_rrm_update_weights_f64 and
+ *               rlvi_wls_solve_f64 instead.  flag 2, nothing written: a loss is not finite.  flag 3: a root-find hit its
+ *               200 evaluations (RLVI_ST_NOCONV in the workspace; the results are written).
+ *               eps outside (0, 1) or (1 - eps) n <= 1: RLVI_E_SHAPE.
+ *   rlvi_rrm_linear_regression_batch_f64    the sweep of main.py:261-273 around rrm.linear_regression (:269).
+ *
+ *   rlvi_huber_linear_regression_f64    standard-learning/huber.py:13-40: theta0 = (X^T X)^-1 X^T y with X^T X formed
+ *               and factored ONCE; then { r = y - X theta0, r_psi = r clipped at c sigma0 (:23), sigma = ||r_psi|| /
+ *               sqrt(2 n alpha) (:25), r_psi = r clipped at c sigma (:27), theta = theta0 + (X^T X)^-1 X^T r_psi
+ *               (:30-32); while ||theta - theta0|| / ||theta0|| > 1e-6: sigma0 = sigma, theta0 = theta }.  The reference's
+ *               `while True` is capped at `maxiter` iterations (its default here: 1000); maxiter = 0: theta0, sigma0.
+ *               alpha = rlvi_huber_alpha(c).  theta [d], scale [1] (the last sigma).
+ *               info = { iterations, 0, 0, flag }.  flag 1, nothing written: X^T X has a pivot that is not safely
+ *               positive (numpy.linalg.solve raises at huber.py:17).  flag 2, nothing written: a scale that is not
+ *               positive and finite (an exactly interpolating fit: sigma = 0) or a theta that is not finite.  flag 3:
+ *               the iteration still moved when the cap was reached (RLVI_ST_NOCONV; the last iterate is written).
+ *               c <= 0 or sigma0 <= 0: RLVI_E_SHAPE.
+ *   rlvi_huber_linear_regression_batch_f64  the sweep of main.py:261-273 around huber.linear_regression (:266);
+ *               scale [B].
+ *   rlvi_huber_alpha    huber.py:15, c^2 (1 - F1(c^2)) + F3(c^2) with the chi-square distribution functions in closed
+ *               form: F1(c^2) = erf(c / sqrt 2), F3(c^2) = F1(c^2) - sqrt(2 / pi) c exp(-c^2 / 2).  Host only.
+ * Return codes: RLVI_E_NULL, RLVI_E_SHAPE (batch, n, d <= 0, maxiter < 0, the parameters above), RLVI_E_LIMIT (n > 4096,
+ * d > 31, batch > 1 048 576), RLVI_E_ALIGN, in this order.  Graph-capturable; no host synchronisation.
+ * ------------------------------------------------------------------------------------- */
+double rlvi_huber_alpha(double c);
+int rlvi_rrm_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double eps, int maxiter,
+                                   double tol, double *theta, double *weights, int32_t *info, void *ws, void *stream);
+int rlvi_rrm_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                         double eps, int maxiter, double tol, double *theta, double *weights,
+                                         int32_t *info, void *ws, void *stream);
+int rlvi_huber_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double c, double sigma0,
+                                     int maxiter, double *theta, double *scale, int32_t *info, void *ws, void *stream);
+int rlvi_huber_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                           double c, double sigma0, int maxiter, double *theta, double *scale,
+                                           int32_t *info, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

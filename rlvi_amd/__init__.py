@@ -10,3 +10,21 @@ __version__ = "0.2.0"
 # hipIpcGetMemHandle fails with "invalid argument".  The ROCm runtime reads the variable when it starts
 # (the first GPU call of the process), so it is defaulted here, at import time, and never overridden.
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+
+# The robust linear regressions of the reference's comparison (standard-learning/main.py:248-357) beside
+# standard.linear_regression, resolved on first use: importing the package stays free of torch.
+_ESTIMATORS = {
+    "rrm_linear_regression": ("rrm", "linear_regression"),
+    "rrm_linear_regression_batch": ("rrm", "linear_regression_batch"),
+    "huber_linear_regression": ("huber", "linear_regression"),
+    "huber_linear_regression_batch": ("huber", "linear_regression_batch"),
+}
+__all__ = sorted(_ESTIMATORS)
+
+
+def __getattr__(name):
+    if name in _ESTIMATORS:
+        import importlib
+        module, attr = _ESTIMATORS[name]
+        return getattr(importlib.import_module("." + module, __name__), attr)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,7 +13,8 @@
 // linreg_rlvi_kernel (standard.hip) is held to the instructions it had: it takes the offsets, the pivot floor and
 // sl_block_sum2 from here and keeps the Gram collection, the solve, the fixed point and the stop test in place --
 // each of them called from here moves its register allocation, and single cells of its sweep by up to 2 % either way
-// (profiles/r17_sl_header.md).
+// (profiles/r17_sl_header.md).  Its fit (sl_wls, sl_residuals: that text, verbatim) lives in rlvi_linreg.h, which the
+// RRM and Huber regressions (robust_linreg.hip) share; RRM's weight rule is rlvi_rrm.h.
 #pragma once
 #include <initializer_list>
 

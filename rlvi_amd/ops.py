@@ -866,6 +866,63 @@ def rrm_update_weights(losses, eps, out=None, info=None, ws=None):
     return _one_launch("rlvi_rrm_update_weights_f64", (losses,), (float(eps),), ((out, losses.shape[0]),), info, ws)
 
 
+# ---- the robust linear regressions of standard-learning/main.py:248-357 (robust_linreg.hip)
+def _linreg_inputs(X, y):
+    _require_gpu(X, y)
+    if not (_fp64(X, dims=2) and _fp64(y, numel=X.shape[0])):
+        raise ValueError("X [n, d] and y [n] must be contiguous fp64 device tensors")
+    return X.shape
+
+
+def rrm_linear_regression(X, y, eps, maxiter=100, tol=1e-3, out=None, info=None, ws=None):
+    """linear_regression(X, y, eps, maxiter, tol) of standard-learning/rrm.py:55-73 as ONE launch on device tensors
+    (rlvi_rrm_linear_regression_f64; no host synchronisation here).  out: (theta [d], weights [n]) to write into, or
+    None.  Returns (theta, weights, info int32[4] = {outer iterations, evaluations of the last root-find, evaluations in
+    all, flag}); flag 1 (a pivot not safely positive: compose rrm_update_weights / wls_solve instead) and flag 2 (a
+    loss not finite): nothing was written; flag 3: a root-find hit its 200 evaluations (RLVI_ST_NOCONV in ws)."""
+    n, d = _linreg_inputs(X, y)
+    theta, weights = out if out is not None else (None, None)
+    return _one_launch("rlvi_rrm_linear_regression_f64", (X, y), (float(eps), int(maxiter), float(tol)),
+                       ((theta, d), (weights, n)), info, ws)
+
+
+def rrm_linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, out=None, info=None, ws=None):
+    """B calls of rrm_linear_regression (the sweep of main.py:261-273) as ONE launch
+    (rlvi_rrm_linear_regression_batch_f64): X [B, n, d], y [B, n], one eps for all -> (theta [B, d], weights [B, n],
+    info int32[B, 4]); problem b has the bits of its single call."""
+    B, n, d = _batch_shape("X", X, y)
+    theta, weights = out if out is not None else (None, None)
+    theta, weights, info = _one_launch("rlvi_rrm_linear_regression_batch_f64", (X, y),
+                                       (float(eps), int(maxiter), float(tol)),
+                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
+    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+
+
+def huber_linear_regression(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=None, info=None, ws=None):
+    """linear_regression(X, y, c, sigma0) of standard-learning/huber.py:13-40 as ONE launch on device tensors
+    (rlvi_huber_linear_regression_f64; no host synchronisation here); the reference's `while True` is capped at
+    maxiter.  out: (theta [d], scale [1]) to write into, or None.  Returns (theta, scale -- the last sigma --, info
+    int32[4] = {iterations, 0, 0, flag}); flag 1 (X^T X singular) and flag 2 (a scale not positive and finite, a theta
+    not finite): nothing was written; flag 3: the cap was reached while the iteration still moved (RLVI_ST_NOCONV in
+    ws, the last iterate written)."""
+    n, d = _linreg_inputs(X, y)
+    theta, scale = out if out is not None else (None, None)
+    return _one_launch("rlvi_huber_linear_regression_f64", (X, y), (float(c), float(sigma0), int(maxiter)),
+                       ((theta, d), (scale, 1)), info, ws)
+
+
+def huber_linear_regression_batch(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=None, info=None, ws=None):
+    """B calls of huber_linear_regression (the sweep of main.py:261-273) as ONE launch
+    (rlvi_huber_linear_regression_batch_f64): X [B, n, d], y [B, n], one c and sigma0 for all -> (theta [B, d], scale
+    [B], info int32[B, 4]); problem b has the bits of its single call."""
+    B, n, d = _batch_shape("X", X, y)
+    theta, scale = out if out is not None else (None, None)
+    theta, scale, info = _one_launch("rlvi_huber_linear_regression_batch_f64", (X, y),
+                                     (float(c), float(sigma0), int(maxiter)),
+                                     _batch_outs(B, (theta, d), (scale, 1)), info, ws)
+    return theta.view(B, d), scale.view(B), info.view(B, 4)
+
+
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,
                          iters=None):
     """One mini-batch of online-learning/main.py:293-297 in ONE launch on device tensors: residuals =

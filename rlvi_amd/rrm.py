@@ -5,14 +5,16 @@ the reference's names and argument order.
     mean(sample, eps, maxiter=100, tol=1e-3)                          reference rrm.py:36-52
     pca(sample, eps, maxiter=100, tol=1e-2, theta_init=None)          reference rrm.py:94-107
     covariance(sample, eps, maxiter=100, tol=1e-2)                    reference rrm.py:110-124
+    linear_regression(X, y, eps, maxiter=100, tol=1e-3)               reference rrm.py:55-73
     mean_batch / pca_batch / covariance_batch                         the loops of reference main.py:180-188, :489-494,
                                                                       :539-544: B problems of one shape in ONE launch
+    linear_regression_batch                                           the sweep of reference main.py:261-273
 
 Every estimator is ONE launch of moments.hip (rlvi_rrm_*_f64) between one pinned copy in and one out, through the
 staging helpers of rlvi_amd.standard; there is no host loop.  The weight rule returns the exact minimiser of the
 reference's objective (the root of "entropy of w = log((1 - eps) n)") where the reference stops at Brent's tolerance:
-the two agree to about 1e-8 in theta, not to the bit.  linear_regression and logistic_regression under RRM
-are not mirrored.  return_info: (theta, weights, info int32[4] = {outer iterations, evaluations of the last root-find,
+the two agree to about 1e-8 in theta, not to the bit.  linear_regression (below) is ONE launch of
+robust_linreg.hip; logistic_regression under RRM is not mirrored.  return_info: (theta, weights, info int32[4] = {outer iterations, evaluations of the last root-find,
 evaluations in all -- pca: Jacobi sweeps in all --, flag}).
 """
 import numpy as np
@@ -73,3 +75,119 @@ def pca_batch(sample, eps, maxiter=100, tol=1e-2, theta_init=None, *, return_inf
 def covariance_batch(sample, eps, maxiter=100, tol=1e-2, *, return_info=False):
     """B calls of covariance as ONE launch: sample [B, n, d], ONE eps for all problems -> theta [B, d, d]."""
     return _std._moments_batch("covariance", sample, maxiter, tol, return_info, eps=eps, rrm=True)
+
+
+def _linreg_inputs(what, X, y):
+    Xh = np.ascontiguousarray(X, dtype=np.float64)
+    yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
+        raise ValueError("X must be [n, d] and y [n]")
+    # what scipy's lstsq (check_finite) raises at rrm.py:58, before anything reaches the device
+    if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
+        raise ValueError("array must not contain infs or NaNs")
+    n, d = Xh.shape
+    if n == 0 or d == 0 or not ops.linear_regression_check(n, d):
+        raise _lib.RlviError(f"{what} takes n <= 4096 samples and 1 <= d <= 31 features in its one launch: got "
+                             f"n = {n}, d = {d}")
+    return Xh, yh, n, d
+
+
+def _linear_regression_host_loop(X, y, eps, maxiter, tol, ws):
+    """The general path of linear_regression (a design the one launch reports as rank-deficient: the reference's lstsq
+    returns the minimum-norm solution there): one launch per statement of rrm.py:56-71 and the stop test on the host.
+    X, y: device tensors.  Returns (theta, weights, outer) as numpy arrays."""
+    import torch
+    n = X.shape[0]
+    w = torch.full((n,), 1.0 / n, dtype=torch.float64, device=X.device)
+    theta = _std._wls(X, y, w)                                       # rrm.py:57-58
+    losses = (y - X @ theta) ** 2                                    # rrm.py:59
+    outer = 0
+    for _ in range(maxiter):
+        outer += 1
+        w, inf = ops.rrm_update_weights(losses, eps, ws=ws)          # rrm.py:62
+        flag = int(inf[3])
+        if flag == 1:
+            ws.clear_status()
+            raise ValueError("array must not contain infs or NaNs")
+        if flag == 2:
+            ws.raise_on_status("rrm.linear_regression", mask=_lib.ST_NOCONV)
+        prev = theta
+        theta = _std._wls(X, y, w)                                   # rrm.py:65-66
+        losses = (y - X @ theta) ** 2                                # rrm.py:67
+        if bool(torch.linalg.norm(theta - prev) / torch.linalg.norm(prev) <= tol):     # rrm.py:69-71
+            break
+    th = theta.cpu().numpy()
+    ws.raise_on_status("rrm.linear_regression", mask=_lib.ST_TIMEOUT | _lib.ST_NOCONV)
+    ws.clear_status()                                                # (RLVI_ST_SINGULAR is information here)
+    if not np.isfinite(th).all():
+        raise ValueError("array must not contain infs or NaNs")
+    return th, w.cpu().numpy(), outer
+
+
+def linear_regression(X, y, eps, maxiter=100, tol=1e-3, *, return_info=False):
+    """rrm.py:55-73 in ONE launch (n <= 4096, d <= 31: RlviError beyond).  A design the launch reports as
+    rank-deficient -- or one that weights of exactly 0 make so -- is recomputed by the general path (ops.rrm_update_weights
+    + the minimum-norm least-squares solve, one launch per statement), as the reference's lstsq handles it; info is
+    then {its outer iterations, 0, 0, 1}."""
+    Xh, yh, n, d = _linreg_inputs("rrm.linear_regression", X, y)
+    _std._rrm_eps("rrm.linear_regression", eps, n)
+    dev = _std._dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, (Xd, yd) = _std._one_launch_roundtrip(
+        dev, "rrm_linreg", [(Xh, n * d), (yh, n)], d, n,
+        lambda v, out: ops.rrm_linear_regression(v[0].view(n, d), v[1], eps, maxiter=maxiter, tol=tol,
+                                                 out=(out["theta"], out["weights"]), info=out["info"], ws=ws))
+    inf = inf.copy()
+    if inf[3] == 1:
+        th, wh, outer = _linear_regression_host_loop(Xd.view(n, d), yd, eps, maxiter, tol, ws)
+        return (th, wh, np.array([outer, 0, 0, 1], np.int32)) if return_info else th
+    if inf[3] == 2:
+        raise ValueError("array must not contain infs or NaNs")
+    if inf[3] == 3:
+        ws.raise_on_status("rrm.linear_regression", mask=_lib.ST_NOCONV)
+    return (theta.copy(), w.copy(), inf) if return_info else theta.copy()
+
+
+def linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, *, return_info=False):
+    """B calls of linear_regression (the sweep of main.py:261-273) as ONE launch: X [B, n, d], y [B, n], one eps for
+    all -> theta [B, d]; every problem has the bits of its single one-launch call.  A flagged problem raises what the
+    single call's launch reports for it (flag 1: a rank-deficient design -- the batch form has no general path), naming
+    the problem; with return_info (theta, weights [B, n], info int32[B, 4]) nothing is raised and its rows are NaN."""
+    Xh, yh, B, n, d = _std._batch_inputs("X", X, y, nonfinite="array must not contain infs or NaNs")
+    if n == 0 or d == 0 or not ops.linear_regression_check(n, d):
+        raise _lib.RlviError(f"rrm.linear_regression_batch takes n <= 4096 samples and 1 <= d <= 31 features in its one "
+                             f"launch: got n = {n}, d = {d}")
+    _std._rrm_eps("rrm.linear_regression_batch", eps, n)
+    dev = _std._dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, _ = _std._one_launch_roundtrip(
+        dev, "rrm_linreg_batch", [(Xh, B * n * d), (yh, B * n)], d, n,
+        lambda v, out: ops.rrm_linear_regression_batch(v[0].view(B, n, d), v[1].view(B, n), eps, maxiter=maxiter,
+                                                       tol=tol, out=(out["theta"], out["weights"]), info=out["info"],
+                                                       ws=ws), batch=B)
+    inf = inf.copy().reshape(B, 4)
+    _linreg_batch_flags("rrm.linear_regression_batch", ws, inf, return_info,
+                        {1: "a rank-deficient design (rrm.linear_regression takes its general path there)",
+                         2: "array must not contain infs or NaNs"})
+    return _std._batch_results(theta, w, inf, B, (d,), n, return_info)
+
+
+def _linreg_batch_flags(kind, ws, inf, return_info, value_errors):
+    """The convention of standard._batch_flags for kernels whose cap is flag 3: with return_info nothing is raised (the
+    caller blanks the flagged rows); otherwise the lowest flagged problem raises -- ValueError with its text for the
+    flags of `value_errors`, RlviError through the sticky status for flag 3.  The status word is cleared either way."""
+    flagged = np.flatnonzero(inf[:, 3] != 0)
+    if flagged.size == 0:
+        return
+    b = int(flagged[0])
+    flag = int(inf[b, 3])
+    if return_info or flag in value_errors:
+        if (inf[:, 3] == 3).any():
+            ws.clear_status()
+        if return_info:
+            return
+        raise ValueError(f"{kind}: {value_errors[flag]} (problem {b})")
+    try:
+        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
+    except _lib.RlviError as e:
+        raise _lib.RlviError(f"{e} (problem {b})") from None
