@@ -710,6 +710,36 @@ int rlvi_huber_linear_regression_batch_f64(const double *X, const double *y, int
                                            int32_t *info, void *ws, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * RRM's logistic regression, the third curve of the reference's logistic comparison (standard-learning/main.py:
+ * 361-470), as ONE launch (robust_logreg.hip): the workgroup, the fit, the limits (n <= 4096, 1 <= d <= 30) and the
+ * batch convention of rlvi_logistic_regression_f64 / _batch_f64 above, the weight rule of rlvi_rrm_update_weights_f64.
+ *
+ *   rlvi_rrm_logistic_regression_f64    standard-learning/rrm.py:76-91 on utils.py:61-73: weights = 1 / n, (theta,
+ *               losses) = the fit (:77-78); then up to `maxiter` times { update_weights(losses, eps) (:81) -- the exact
+ *               entropy root --, the fit with C weights / max weights (:84, utils.py:66), stop when ||theta - prev|| /
+ *               ||prev|| <= tol (:87-89; a zero ||prev|| gives NaN and no stop, as there) }.  Reaching maxiter is silent,
+ *               as in the reference; maxiter = 0: the bits of rlvi_logistic_fit_f64 with unit weights.  The losses are
+ *               log(1 + exp(z)) for EVERY sample (utils.py:62-64).  X [n, d] row-major, y [n] of 0.0 / 1.0, C > 0 (the
+ *               reference: 1e2).  theta [d + 1] = (intercept, coef ...), weights [n] (the last rule's output: they sum
+ *               to 1; 1 / n with maxiter = 0), info int32[4] = { outer iterations, evaluations of the last root-find,
+ *               Newton steps in all, flag }.
+ *               flag 1, nothing written: a label that is neither 0 nor 1, or a value that is not finite.  flag 2: a fit
+ *               ended at its 50 Newton steps or without an acceptable Armijo step.  flag 3: a root-find hit its 200
+ *               evaluations.  For 2 and 3 RLVI_ST_NOCONV is raised in the workspace and the results are written.
+ *   rlvi_rrm_logistic_regression_batch_f64    the sweep of main.py:372-401 around rrm.logistic_regression (:382): X [B, n, d],
+ *               y [B, n], theta [B, d + 1], weights [B, n], info int32[B, 4]; problem b has the bits of the single entry.
+ * Return codes: RLVI_E_NULL, RLVI_E_SHAPE (batch, n, d <= 0, maxiter < 0, C <= 0, eps outside (0, 1) or
+ * (1 - eps) n <= 1), RLVI_E_LIMIT (n > 4096, d > 30, batch > 1 048 576), RLVI_E_ALIGN, in this order.
+ * Graph-capturable; no host synchronisation.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_rrm_logistic_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double eps, int maxiter,
+                                     double tol, double C, double *theta, double *weights, int32_t *info, void *ws,
+                                     void *stream);
+int rlvi_rrm_logistic_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
+                                           double eps, int maxiter, double tol, double C, double *theta,
+                                           double *weights, int32_t *info, void *ws, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * One mini-batch of the online path in ONE launch, replaces online-learning/main.py:293-297:
  *   log_proba = log(0.5) for the first batch (first != 0; X, w may be NULL), else clf.predict_log_proba(X)[:, 1]
  *   = log sigmoid(X w + b) (:295, X.w on the fp64 matrix cores); residuals = -log_proba (:296 with :84-85: the

@@ -12,8 +12,11 @@ __version__ = "0.2.0"
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 # The robust linear regressions of the reference's comparison (standard-learning/main.py:248-357) beside
-# standard.linear_regression, resolved on first use: importing the package stays free of torch.
+# standard.linear_regression, and RRM's logistic regression (main.py:361-470), resolved on first use: importing the
+# package stays free of torch.
 _ESTIMATORS = {
+    "rrm_logistic_regression": ("rrm", "logistic_regression"),
+    "rrm_logistic_regression_batch": ("rrm", "logistic_regression_batch"),
     "rrm_linear_regression": ("rrm", "linear_regression"),
     "rrm_linear_regression_batch": ("rrm", "linear_regression_batch"),
     "huber_linear_regression": ("huber", "linear_regression"),

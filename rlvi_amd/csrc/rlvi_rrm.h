@@ -1,6 +1,6 @@
 // Robust Risk Minimization's weight rule (standard-learning/rrm.py:12-33) as an exact root, ONE copy: moments.hip (mean,
-// PCA, covariance, the rule on its own) and robust_linreg.hip (linear regression) call it, each with the stride of its
-// own slot area.
+// PCA, covariance, the rule on its own), robust_linreg.hip (linear regression) and robust_logreg.hip (logistic
+// regression) call it, each with the stride of its own slot area.
 #pragma once
 #include "rlvi_sl.h"
 
@@ -10,7 +10,10 @@ constexpr int MO_ROOT_CAP = 200;                   // evaluations of one root-fi
 constexpr double MO_XI_MIN = -700.0, MO_XI_MAX = 700.0;   // xi = log alpha of the RRM rule: alpha stays a normal number
 constexpr double MO_TMAX = 800.0;                  // exp(-800) is 0: a larger l / alpha is cut here (phi t = 0, never 0 inf)
 
-// rrm.update_weights (rrm.py:12-33) on this thread's samples.  The reference minimises g(alpha) = alpha (log sum_i
+// the eps the RRM regressions' entries take (what rlvi_amd.standard._rrm_eps accepts): RLVI_E_SHAPE otherwise
+inline bool rl_eps_ok(double eps, int64_t n) { return eps > 0.0 && eps < 1.0 && (1.0 - eps) * (double)n > 1.0; }
+
+// rrm.update_weights (rrm.py:12-33) on this thread's samples. The reference minimises g(alpha) = alpha (log sum_i
 // exp(-l_i / alpha) - log((1 - eps) n)) over alpha = exp(xi) by scipy's Brent search and returns w_i = exp(-l_i / alpha)
 // / sum_j exp(-l_j / alpha).  g is convex and stationary where the entropy of w equals log((1 - eps) n):
 //     H(xi) = log S + (sum phi_i t_i) / S = log((1 - eps) n),  t_i = (l_i - min l) / alpha, phi_i = exp(-t_i), S = sum phi_i

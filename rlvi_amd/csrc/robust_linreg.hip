@@ -516,9 +516,6 @@ static int rl_args(const double *X, const double *y, int64_t batch, int64_t n, i
     if (batch > SL_MAXBATCH || n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
     return sl_misaligned({X, y, theta, out2}, info, ws) ? RLVI_E_ALIGN : 0;
 }
-// what rlvi_amd.standard._rrm_eps accepts
-static bool rl_eps_ok(double eps, int64_t n) { return eps > 0.0 && eps < 1.0 && (1.0 - eps) * (double)n > 1.0; }
-
 }  // namespace rlvi
 
 using namespace rlvi;

@@ -923,6 +923,32 @@ def huber_linear_regression_batch(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=
     return theta.view(B, d), scale.view(B), info.view(B, 4)
 
 
+# ---- RRM's logistic regression of standard-learning/main.py:361-470 (robust_logreg.hip)
+def rrm_logistic_regression(X, y, eps, maxiter=100, tol=1e-2, C=100.0, out=None, info=None, ws=None):
+    """logistic_regression(X, y, eps, maxiter, tol) of standard-learning/rrm.py:76-91 as ONE launch on device tensors
+    (rlvi_rrm_logistic_regression_f64; no host synchronisation here).  out: (theta [d + 1], weights [n]) to write
+    into, or None.  Returns (theta = (intercept, coef), weights, info int32[4] = {outer iterations, evaluations of the
+    last root-find, Newton steps in all, flag}); flag 1 (a label not 0 / 1, a value not finite): nothing was written;
+    flag 2 (a fit at its Newton cap or without an acceptable step) and flag 3 (a root-find at its 200 evaluations):
+    RLVI_ST_NOCONV in ws, the results written."""
+    n, d = _logistic_inputs(X, y)
+    theta, weights = out if out is not None else (None, None)
+    return _one_launch("rlvi_rrm_logistic_regression_f64", (X, y), (float(eps), int(maxiter), float(tol), float(C)),
+                       ((theta, d + 1), (weights, n)), info, ws)
+
+
+def rrm_logistic_regression_batch(X, y, eps, maxiter=100, tol=1e-2, C=100.0, out=None, info=None, ws=None):
+    """B calls of rrm_logistic_regression (the sweep of main.py:372-401) as ONE launch
+    (rlvi_rrm_logistic_regression_batch_f64): X [B, n, d], y [B, n], one eps for all -> (theta [B, d + 1], weights
+    [B, n], info int32[B, 4]); problem b has the bits of its single call."""
+    B, n, d = _batch_shape("X", X, y)
+    theta, weights = out if out is not None else (None, None)
+    theta, weights, info = _one_launch("rlvi_rrm_logistic_regression_batch_f64", (X, y),
+                                       (float(eps), int(maxiter), float(tol), float(C)),
+                                       _batch_outs(B, (theta, d + 1), (weights, n)), info, ws)
+    return theta.view(B, d + 1), weights.view(B, n), info.view(B, 4)
+
+
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,
                          iters=None):
     """One mini-batch of online-learning/main.py:293-297 in ONE launch on device tensors: residuals =

@@ -9,13 +9,17 @@ the reference's names and argument order.
     mean_batch / pca_batch / covariance_batch                         the loops of reference main.py:180-188, :489-494,
                                                                       :539-544: B problems of one shape in ONE launch
     linear_regression_batch                                           the sweep of reference main.py:261-273
+    logistic_regression(X, y, eps, maxiter=100, tol=1e-2)             reference rrm.py:76-91
+    logistic_regression_batch                                         the sweep of reference main.py:372-401
 
 Every estimator is ONE launch of moments.hip (rlvi_rrm_*_f64) between one pinned copy in and one out, through the
 staging helpers of rlvi_amd.standard; there is no host loop.  The weight rule returns the exact minimiser of the
 reference's objective (the root of "entropy of w = log((1 - eps) n)") where the reference stops at Brent's tolerance:
 the two agree to about 1e-8 in theta, not to the bit.  linear_regression (below) is ONE launch of
-robust_linreg.hip; logistic_regression under RRM is not mirrored.  return_info: (theta, weights, info int32[4] = {outer iterations, evaluations of the last root-find,
-evaluations in all -- pca: Jacobi sweeps in all --, flag}).
+robust_linreg.hip, logistic_regression ONE launch of robust_logreg.hip (its fit is the minimiser liblinear approximates:
+theta agrees to liblinear's tolerance).  return_info: (theta, weights, info int32[4] = {outer iterations,
+evaluations of the last root-find, evaluations in all -- pca: Jacobi sweeps, logistic_regression: Newton steps in all --,
+flag}).
 """
 import numpy as np
 
@@ -172,17 +176,84 @@ def linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, *, return_info=Fal
     return _std._batch_results(theta, w, inf, B, (d,), n, return_info)
 
 
-def _linreg_batch_flags(kind, ws, inf, return_info, value_errors):
-    """The convention of standard._batch_flags for kernels whose cap is flag 3: with return_info nothing is raised (the
-    caller blanks the flagged rows); otherwise the lowest flagged problem raises -- ValueError with its text for the
-    flags of `value_errors`, RlviError through the sticky status for flag 3.  The status word is cleared either way."""
+_LOGREG_FLAG1 = ("y must hold the class labels 0 and 1, and the fit must not meet numbers that are not finite (a design "
+                 "scaled beyond what fp64 resolves)")
+
+
+def _logreg_checks(what, yh, n, d, eps, problems=False):
+    """What is raised before anything reaches the device: labels of a single class (sklearn's message, as
+    standard.logistic_regression(solver="newton")), shapes beyond the one launch, eps out of range."""
+    y2 = yh.reshape(-1, n) if n else yh.reshape(1, 0)
+    one = np.ones(len(y2), bool) if n == 0 else y2.min(axis=1) == y2.max(axis=1)
+    if one.any():
+        where = f" (problem {int(np.argmax(one))})" if problems else ""
+        raise ValueError(f"This solver needs samples of at least 2 classes in the data{where}")
+    if d == 0 or not ops.logistic_regression_check(n, d):
+        raise _lib.RlviError(f"{what} takes n <= 4096 samples and 1 <= d <= 30 features in its one launch: got "
+                             f"n = {n}, d = {d}")
+    _std._rrm_eps(what, eps, n)
+
+
+def logistic_regression(X, y, eps, maxiter=100, tol=1e-2, *, return_info=False):
+    """rrm.py:76-91 in ONE launch (n <= 4096, 1 <= d <= 30: RlviError beyond) -> theta [d + 1] = (intercept, coef).
+    Each fit is the minimiser liblinear approximates to its tol = 1e-4 and each weight update the exact root of the
+    rule, so theta agrees with the reference's to liblinear's tolerance, not to the bit.  Reaching maxiter is silent,
+    as in the reference.  return_info: (theta, weights [n], info int32[4] = {outer iterations, evaluations of the last
+    root-find, Newton steps in all, flag})."""
+    Xh = np.ascontiguousarray(X, dtype=np.float64)
+    yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
+        raise ValueError("X must be [n, d] and y [n]")
+    # what sklearn's fit raises a ValueError for (utils.py:68), before anything reaches the device
+    if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
+        raise ValueError("Input contains NaN or infinity.")
+    n, d = Xh.shape
+    _logreg_checks("rrm.logistic_regression", yh, n, d, eps)
+    dev = _std._dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, _ = _std._one_launch_roundtrip(
+        dev, "rrm_logreg", [(Xh, n * d), (yh, n)], d + 1, n,
+        lambda v, out: ops.rrm_logistic_regression(v[0].view(n, d), v[1], eps, maxiter=maxiter, tol=tol,
+                                                   out=(out["theta"], out["weights"]), info=out["info"], ws=ws))
+    inf = inf.copy()
+    if inf[3] == 1:
+        raise ValueError(f"rrm.logistic_regression: {_LOGREG_FLAG1}")
+    if inf[3] in (2, 3):
+        ws.raise_on_status("rrm.logistic_regression", mask=_lib.ST_NOCONV)
+    return (theta.copy(), w.copy(), inf) if return_info else theta.copy()
+
+
+def logistic_regression_batch(X, y, eps, maxiter=100, tol=1e-2, *, return_info=False):
+    """B calls of logistic_regression (the sweep of main.py:372-401) as ONE launch: X [B, n, d], y [B, n] of 0 / 1 with
+    both classes in every problem, one eps for all -> theta [B, d + 1]; every problem has the bits of its single call.
+    A flagged problem raises what its single call raises, naming the problem; with return_info (theta, weights [B, n],
+    info int32[B, 4]) nothing is raised and its rows are NaN."""
+    Xh, yh, B, n, d = _std._batch_inputs("X", X, y)
+    _logreg_checks("rrm.logistic_regression_batch", yh, n, d, eps, problems=True)
+    dev = _std._dev()
+    ws = ops.workspace(dev, n, 0)
+    theta, w, inf, _ = _std._one_launch_roundtrip(
+        dev, "rrm_logreg_batch", [(Xh, B * n * d), (yh, B * n)], d + 1, n,
+        lambda v, out: ops.rrm_logistic_regression_batch(v[0].view(B, n, d), v[1].view(B, n), eps, maxiter=maxiter,
+                                                         tol=tol, out=(out["theta"], out["weights"]),
+                                                         info=out["info"], ws=ws), batch=B)
+    inf = inf.copy().reshape(B, 4)
+    _linreg_batch_flags("rrm.logistic_regression_batch", ws, inf, return_info, {1: _LOGREG_FLAG1}, caps=(2, 3))
+    return _std._batch_results(theta, w, inf, B, (d + 1,), n, return_info)
+
+
+def _linreg_batch_flags(kind, ws, inf, return_info, value_errors, caps=(3,)):
+    """The convention of standard._batch_flags for kernels whose cap is flag 3 (`caps`: the flags that raise
+    RLVI_ST_NOCONV): with return_info nothing is raised (the caller blanks the flagged rows); otherwise the lowest
+    flagged problem raises -- ValueError with its text for the flags of `value_errors`, RlviError through the sticky
+    status for a cap flag.  The status word is cleared either way."""
     flagged = np.flatnonzero(inf[:, 3] != 0)
     if flagged.size == 0:
         return
     b = int(flagged[0])
     flag = int(inf[b, 3])
     if return_info or flag in value_errors:
-        if (inf[:, 3] == 3).any():
+        if np.isin(inf[:, 3], caps).any():
             ws.clear_status()
         if return_info:
             return
