@@ -20,7 +20,10 @@ from . import rrm as _rrm
 from . import standard as _std
 
 _NONFINITE = "array must not contain infs or NaNs"
-_FLAGS = {1: "Singular matrix", 2: _NONFINITE}
+# what the kernel's flags raise (standard._raise_flags): the cap has a message of its own, not the status word's
+_FLAGS = {1: (np.linalg.LinAlgError, "Singular matrix", False), 2: (ValueError, _NONFINITE, False),
+          3: (_lib.RlviError, "{name}: the iteration still moved by more than 1e-6 after maxiter = {maxiter} "
+                              "iterations", True)}
 
 
 def psi_huber(vec, c):
@@ -36,32 +39,17 @@ def _params(what, c, sigma0, maxiter):
         raise ValueError(f"{what} needs maxiter >= 0: got {maxiter}")
 
 
-def _capped(what, ws, maxiter, where=""):
-    ws.clear_status()
-    raise _lib.RlviError(f"{what}: the iteration still moved by more than 1e-6 after maxiter = {maxiter} "
-                         f"iterations{where}")
-
-
 def linear_regression(X, y, c=0.7317, sigma0=1, *, maxiter=1000, return_info=False):
     """huber.py:13-40 in ONE launch (n <= 4096, d <= 31: RlviError beyond).  numpy.linalg.LinAlgError("Singular
     matrix") where numpy.linalg.solve raises it at huber.py:17; ValueError for input that is not finite and for an
     exactly interpolating fit (sigma = 0: the reference's lstsq meets a NaN); RlviError when the cap is reached."""
     Xh, yh, n, d = _rrm._linreg_inputs("huber.linear_regression", X, y)
     _params("huber.linear_regression", c, sigma0, maxiter)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, scale, inf, _ = _std._one_launch_roundtrip(
-        dev, "huber_linreg", [(Xh, n * d), (yh, n)], d, 1,
-        lambda v, out: ops.huber_linear_regression(v[0].view(n, d), v[1], c, sigma0, maxiter=maxiter,
-                                                   out=(out["theta"], out["weights"]), info=out["info"], ws=ws))
-    inf = inf.copy()
-    if inf[3] == 1:
-        raise np.linalg.LinAlgError(_FLAGS[1])
-    if inf[3] == 2:
-        raise ValueError(_NONFINITE)
-    if inf[3] == 3:
-        _capped("huber.linear_regression", ws, maxiter)
-    return (theta.copy(), float(scale[0]), inf) if return_info else theta.copy()
+    theta, scale, inf, _, ws = _std._one_launch_call("huber.linear_regression", ops.huber_linear_regression,
+                                                     [(Xh, (n, d)), (yh, None)], (c, sigma0, maxiter), n, (d,), (),
+                                                     pair=True)
+    _std._raise_flags(ws, inf, return_info, "huber.linear_regression", _FLAGS, maxiter=maxiter)
+    return (theta, float(scale), inf) if return_info else theta
 
 
 def linear_regression_batch(X, y, c=0.7317, sigma0=1, *, maxiter=1000, return_info=False):
@@ -70,29 +58,10 @@ def linear_regression_batch(X, y, c=0.7317, sigma0=1, *, maxiter=1000, return_in
     single call raises for it, naming the problem; with return_info (theta, sigma [B], info int32[B, 4]) nothing is
     raised and its rows are NaN."""
     Xh, yh, B, n, d = _std._batch_inputs("X", X, y, nonfinite=_NONFINITE)
-    if n == 0 or d == 0 or not ops.linear_regression_check(n, d):
-        raise _lib.RlviError(f"huber.linear_regression_batch takes n <= 4096 samples and 1 <= d <= 31 features in its "
-                             f"one launch: got n = {n}, d = {d}")
+    _rrm._linreg_limits("huber.linear_regression_batch", n, d)
     _params("huber.linear_regression_batch", c, sigma0, maxiter)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, scale, inf, _ = _std._one_launch_roundtrip(
-        dev, "huber_linreg_batch", [(Xh, B * n * d), (yh, B * n)], d, 1,
-        lambda v, out: ops.huber_linear_regression_batch(v[0].view(B, n, d), v[1].view(B, n), c, sigma0,
-                                                         maxiter=maxiter, out=(out["theta"], out["weights"]),
-                                                         info=out["info"], ws=ws), batch=B)
-    inf = inf.copy().reshape(B, 4)
-    flagged = np.flatnonzero(inf[:, 3] != 0)
-    if flagged.size and (inf[:, 3] == 3).any():
-        ws.clear_status()
-    if flagged.size and not return_info:
-        b = int(flagged[0])
-        if inf[b, 3] == 1:
-            raise np.linalg.LinAlgError(f"{_FLAGS[1]} (problem {b})")
-        if inf[b, 3] == 2:
-            raise ValueError(f"{_NONFINITE} (problem {b})")
-        _capped("huber.linear_regression_batch", ws, maxiter, f" (problem {b})")
-    if not return_info:
-        return theta.copy().reshape(B, d)
-    theta, scale, inf = _std._batch_results(theta, scale, inf, B, (d,), 1, True)
-    return theta, scale.reshape(B), inf
+    theta, scale, inf, _, ws = _std._one_launch_call("huber.linear_regression_batch", ops.huber_linear_regression_batch,
+                                                     [(Xh, (B, n, d)), (yh, (B, n))], (c, sigma0, maxiter), n, (d,), (),
+                                                     batch=B, pair=True)
+    bad = _std._raise_flags(ws, inf, return_info, "huber.linear_regression_batch", _FLAGS, batch=True, maxiter=maxiter)
+    return _std._results(theta, scale, inf, bad, return_info)

@@ -567,9 +567,126 @@ def _one_launch(entry, inputs, args, outs, info, ws):
     if info is None:
         info = torch.zeros((X.shape[0], 4) if batched else 4, dtype=torch.int32, device=X.device)
     ws = ws or workspace(X.device, X.shape[1 if batched else 0], 0)
-    _lib.check(getattr(L, entry)(*(_ptr(t) for t in inputs), *X.shape, *args, *(_ptr(t) for t in outs), _ptr(info),
+    _lib.check(getattr(L, entry)(*[_ptr(t) for t in inputs], *X.shape, *args, *[_ptr(t) for t in outs], _ptr(info),
                                  ws.ptr, _stream_ptr()), entry)
     return (*outs, info)
+
+
+def _design(what, bad, X, vectors, batched):
+    """The input check of every estimator below: X is a contiguous fp64 device tensor [n, d] -- batched: [B, n, d] --
+    and each of `vectors` one of its n (of its [B, n]) elements.  Returns (B, n, d), B = 1 unbatched.  `bad`: the
+    single form's texts for an X that is not, and for a vector that is not."""
+    _require_gpu(X, *vectors)
+    if batched:
+        if not _fp64(X, dims=3):
+            raise ValueError(f"{what} [B, n, d] must be a contiguous fp64 device tensor")
+        B, n, d = X.shape
+        for v in vectors:
+            if not (_fp64(v, dims=2) and v.shape[0] == B and v.shape[1] == n):
+                raise ValueError(f"y must be a contiguous fp64 device tensor of {what}'s [B, n]")
+        return B, n, d
+    if not _fp64(X, dims=2):
+        raise ValueError(bad[0])
+    n, d = X.shape
+    for v in vectors:
+        if not _fp64(v, numel=n):
+            raise ValueError(bad[1])
+    return 1, n, d
+
+
+def _theta_init(theta_init, d):
+    """the pointer of pca's theta_init [d] (NULL for None), checked"""
+    if theta_init is not None:
+        _require_gpu(theta_init)
+        if not _fp64(theta_init, numel=d):
+            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
+    return _ptr(theta_init)
+
+
+class _Estimator:
+    """A one-launch fp64 estimator with a batch form, written once for both: the stem of its C entries
+    (rlvi_<stem>_f64 and rlvi_<stem>_batch_f64), scalars(n, d, *the wrapper's keyword values) -> the entry's scalar
+    arguments, lengths(n, d) -> the elements of one problem's part of each output, optional: the last output is NULL
+    unless given (where False, one that is not given is allocated), square: the first output is a [d, d] matrix, the
+    design's name in messages and the single form's texts for a bad design and a bad vector.  The batch form is the
+    single form with a leading B: outputs of B x length elements, results viewed [B, ...], info int32[B, 4]."""
+
+    def __init__(self, stem, scalars, lengths, optional=False, square=False, what="X", bad=None):
+        self.entries = (f"rlvi_{stem}_f64", f"rlvi_{stem}_batch_f64")
+        self.scalars, self.lengths, self.optional, self.square, self.what = scalars, lengths, optional, square, what
+        self.bad = bad or (f"{what} [n, d] must be a contiguous fp64 device tensor",
+                           f"y and the weights must be contiguous fp64 device tensors of {what}'s n elements")
+
+    def __call__(self, batched, inputs, values, outs, info, ws):
+        """The single (batched False) or the batch form on the wrapper's inputs, keyword values and output tensors
+        (None: allocated here) -> (first output, second output, info)."""
+        B, n, d = _design(self.what, self.bad, inputs[0], inputs[1:], batched)
+        lengths = self.lengths(n, d)
+        if len(outs) != len(lengths):
+            raise ValueError(f"{len(lengths)} output tensors (or None) are expected, not {len(outs)}")
+        sized = [(t, B * k) for t, k in zip(outs, lengths)]
+        if batched:
+            for t, k in zip(outs, lengths):
+                if t is not None:
+                    _require_gpu(t)
+                    if not _fp64(t, numel=B * k):
+                        raise ValueError(f"an output must be a contiguous fp64 device tensor of {B} x {k} elements")
+        if self.optional and outs[-1] is None:
+            sized[-1] = (None, None)
+        res = _one_launch(self.entries[batched], inputs, self.scalars(n, d, *values), sized, info, ws)
+        first, second, info = res[0], res[1], res[-1]
+        if batched:
+            first, second, info = first.view(B, -1), second.view(B, -1), info.view(B, 4)
+        if self.square:
+            first = first.view(B, d, d) if batched else first.view(d, d)
+        return first, second, info
+
+
+def _theta_weights(n, d):
+    return d, n
+
+
+def _matrix_weights(n, d):
+    return d * d, n
+
+
+def _rlvi_scalars(n, d, maxiter, tol, estep_tol, estep_maxiter):
+    return int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)
+
+
+def _rrm_scalars(n, d, eps, maxiter, tol):
+    return float(eps), int(maxiter), float(tol)
+
+
+_XY_BAD = ("X [n, d] and y [n] must be contiguous fp64 device tensors",) * 2
+_LINREG = _Estimator("linear_regression", _rlvi_scalars, _theta_weights, bad=_XY_BAD)
+_LOGREG = _Estimator("logistic_regression",
+                     lambda n, d, maxiter, tol, estep_tol, estep_maxiter, C:
+                     (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter), float(C)),
+                     lambda n, d: (d + 1, n, n), optional=True)          # (losses)
+_MEAN = _Estimator("robust_mean", _rlvi_scalars, _theta_weights, what="sample")
+_PCA = _Estimator("robust_pca",
+                  lambda n, d, maxiter, tol, theta_init, estep_tol, estep_maxiter:
+                  (int(maxiter), float(tol), _theta_init(theta_init, d), float(estep_tol), int(estep_maxiter)),
+                  _theta_weights, what="sample")
+_COVARIANCE = _Estimator("robust_covariance",
+                         lambda n, d, n_eff, maxiter, tol, estep_tol, estep_maxiter:
+                         (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
+                         _matrix_weights, square=True, what="sample")
+_RRM_MEAN = _Estimator("rrm_mean", _rrm_scalars, _theta_weights, what="sample")
+_RRM_PCA = _Estimator("rrm_pca",
+                      lambda n, d, eps, maxiter, tol, theta_init:
+                      (float(eps), int(maxiter), float(tol), _theta_init(theta_init, d)),
+                      _theta_weights, what="sample")
+_RRM_COVARIANCE = _Estimator("rrm_covariance", _rrm_scalars, _matrix_weights, square=True, what="sample")
+_RRM_LINREG = _Estimator("rrm_linear_regression", _rrm_scalars, _theta_weights, bad=_XY_BAD)
+_HUBER_LINREG = _Estimator("huber_linear_regression",
+                           lambda n, d, c, sigma0, maxiter: (float(c), float(sigma0), int(maxiter)),
+                           lambda n, d: (d, 1), bad=_XY_BAD)
+_RRM_LOGREG = _Estimator("rrm_logistic_regression",
+                         lambda n, d, eps, maxiter, tol, C: (float(eps), int(maxiter), float(tol), float(C)),
+                         lambda n, d: (d + 1, n))
+_NO_OUT = (None, None)
 
 
 def linear_regression(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None,
@@ -578,27 +695,12 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter
     (no host synchronisation here).  Returns (theta [d], weights [n], info int32[4] = {outer iterations, inner
     iterations of the last E-step, inner iterations in all, fallback}) -- info[3] == 1 (rank-deficient design):
     theta / weights were not written, compose wls_solve / linreg_losses / update_weights_f64 instead."""
-    _require_gpu(X, y)
-    if not (_fp64(X) and _fp64(y)):
-        raise ValueError("X [n, d] and y [n] must be contiguous fp64 device tensors")
-    n, d = X.shape
-    return _one_launch("rlvi_linear_regression_f64", (X, y),
-                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _LINREG(False, (X, y), (maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def logistic_regression_check(n, d):
     """True if rlvi_logistic_regression_f64 / rlvi_logistic_fit_f64 take an [n, d] design (n <= 4096, d <= 30)."""
     return _lib.load().rlvi_logistic_regression_check(int(n), int(d)) == 0
-
-
-def _logistic_inputs(X, *vectors):
-    _require_gpu(X, *vectors)
-    if not _fp64(X, dims=2):
-        raise ValueError("X [n, d] must be a contiguous fp64 device tensor")
-    if not all(_fp64(v, numel=X.shape[0]) for v in vectors):
-        raise ValueError("y and the weights must be contiguous fp64 device tensors of X's n elements")
-    return X.shape
 
 
 def logistic_fit(X, y, w, C=100.0, theta=None, losses=None, info=None, ws=None):
@@ -608,7 +710,7 @@ def logistic_fit(X, y, w, C=100.0, theta=None, losses=None, info=None, ws=None):
     (intercept, coef), losses [n] = log(1 + exp(z)), info int32[4] = {0, 0, Newton steps, flag}); flag 1: nothing
     was written (data not finite, y not 0 / 1, no positive weight, a pivot not safely positive); flag 2: the Newton cap, or a line search
     without an acceptable step (RLVI_ST_NOCONV in ws)."""
-    n, d = _logistic_inputs(X, y, w)
+    _, n, d = _design("X", _LOGREG.bad, X, (y, w), False)
     return _one_launch("rlvi_logistic_fit_f64", (X, y, w), (float(C),), ((theta, d + 1), (losses, n)), info, ws)
 
 
@@ -618,12 +720,7 @@ def logistic_regression(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxit
     (rlvi_logistic_regression_f64; no host synchronisation here).  Returns (theta [d + 1] = (intercept, coef),
     weights [n], info int32[4] = {outer iterations, inner iterations of the last E-step, Newton steps in all, flag});
     `losses` [n], if given, receives the last fit's.  flag as logistic_fit."""
-    n, d = _logistic_inputs(X, y)
-    theta, weights, _, info = _one_launch(
-        "rlvi_logistic_regression_f64", (X, y),
-        (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter), float(C)),
-        ((theta, d + 1), (weights, n), (losses, None)), info, ws)
-    return theta, weights, info
+    return _LOGREG(False, (X, y), (maxiter, tol, estep_tol, estep_maxiter, C), (theta, weights, losses), info, ws)
 
 
 def moments_check(n, d):
@@ -632,23 +729,13 @@ def moments_check(n, d):
     return _lib.load().rlvi_moments_check(int(n), int(d)) == 0
 
 
-def _sample_shape(sample):
-    _require_gpu(sample)
-    if not _fp64(sample, dims=2):
-        raise ValueError("sample [n, d] must be a contiguous fp64 device tensor")
-    return sample.shape
-
-
 def robust_mean(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None, info=None,
                 ws=None):
     """mean(sample, maxiter, tol) of standard-learning/rlvi.py:46-65 as ONE launch on device tensors
     (rlvi_robust_mean_f64; no host synchronisation here).  Returns (theta [d], weights [n], info int32[4] = {outer
     iterations, inner iterations of the last E-step, inner iterations in all, flag}); flag 1: nothing was written
     (data not finite, a variance not safely positive)."""
-    n, d = _sample_shape(sample)
-    return _one_launch("rlvi_robust_mean_f64", (sample,),
-                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _MEAN(False, (sample,), (maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def robust_pca(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, estep_maxiter=100, theta=None,
@@ -657,14 +744,7 @@ def robust_pca(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, e
     (rlvi_robust_pca_f64).  theta_init [d] (fp64, on the device) replaces the first fit and is used as is.  Returns
     (theta [d], weights [n], info = {outer, inner of the last E-step, Jacobi sweeps in all, flag}); flag 2: an
     eigen-solve hit its 30 sweeps (RLVI_ST_NOCONV in ws)."""
-    if theta_init is not None:
-        _require_gpu(theta_init)
-        if not _fp64(theta_init, numel=sample.shape[1]):
-            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
-    n, d = _sample_shape(sample)
-    return _one_launch("rlvi_robust_pca_f64", (sample,),
-                       (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _PCA(False, (sample,), (maxiter, tol, theta_init, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, theta=None,
@@ -673,48 +753,17 @@ def robust_covariance(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, este
     launch on device tensors (rlvi_robust_covariance_f64).  Returns (theta [d, d], weights [n], info = {outer, inner
     of the last E-step, E-steps with the constraint active, flag}); flag 1: nothing was written (data not finite, a
     pivot not safely positive, n_eff outside (0, n)); flag 2: a root-find hit its cap (RLVI_ST_NOCONV in ws)."""
-    n, d = _sample_shape(sample)
-    theta, weights, info = _one_launch(
-        "rlvi_robust_covariance_f64", (sample,),
-        (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-        ((None if theta is None else theta.view(-1), d * d), (weights, n)), info, ws)
-    return theta.view(d, d), weights, info
+    return _COVARIANCE(False, (sample,), (n_eff, maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 # ---- a Monte-Carlo sweep in ONE launch: B problems of one shape, one workgroup each.  The single forms' keywords; the
 # arrays carry a leading batch dimension; problem b gets the bits of the single call on it alone.
-def _batch_shape(what, X, *vectors):
-    """(B, n, d) of a batch [B, n, d] and its [B, n] vectors, all contiguous fp64 device tensors"""
-    _require_gpu(X, *vectors)
-    if not _fp64(X, dims=3):
-        raise ValueError(f"{what} [B, n, d] must be a contiguous fp64 device tensor")
-    if not all(_fp64(v, dims=2) and tuple(v.shape) == tuple(X.shape[:2]) for v in vectors):
-        raise ValueError(f"y must be a contiguous fp64 device tensor of {what}'s [B, n]")
-    return X.shape
-
-
-def _batch_outs(B, *outs):
-    """[(tensor or None, rows' length)] -> _one_launch's outs, a given tensor checked to be [B, length] elements"""
-    res = []
-    for t, k in outs:
-        if t is not None:
-            _require_gpu(t)
-            if not _fp64(t, numel=B * k):
-                raise ValueError(f"an output must be a contiguous fp64 device tensor of {B} x {k} elements")
-        res.append((t, B * k))
-    return res
-
-
 def linear_regression_batch(X, y, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None,
                             weights=None, info=None, ws=None):
     """B linear regressions (linear_regression above; the loop of standard-learning/main.py:261-273) as ONE launch
     (rlvi_linear_regression_batch_f64): X [B, n, d], y [B, n] -> (theta [B, d], weights [B, n], info int32[B, 4]).
     info[b, 3] == 1: problem b is rank-deficient, its rows were not written -- the general path is the caller's."""
-    B, n, d = _batch_shape("X", X, y)
-    theta, weights, info = _one_launch("rlvi_linear_regression_batch_f64", (X, y),
-                                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _LINREG(True, (X, y), (maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, C=100.0, theta=None,
@@ -722,41 +771,21 @@ def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, estep_tol=1e-3, estep
     """B logistic regressions (logistic_regression above; main.py:431-437) as ONE launch
     (rlvi_logistic_regression_batch_f64): X [B, n, d], y [B, n] -> (theta [B, d + 1], weights [B, n], info
     int32[B, 4]); `losses` [B, n], if given, receives the last fits'."""
-    B, n, d = _batch_shape("X", X, y)
-    if losses is not None:
-        (losses, _), = _batch_outs(B, (losses, n))
-    theta, weights, _, info = _one_launch(
-        "rlvi_logistic_regression_batch_f64", (X, y),
-        (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter), float(C)),
-        _batch_outs(B, (theta, d + 1), (weights, n)) + [(losses, None)], info, ws)
-    return theta.view(B, d + 1), weights.view(B, n), info.view(B, 4)
+    return _LOGREG(True, (X, y), (maxiter, tol, estep_tol, estep_maxiter, C), (theta, weights, losses), info, ws)
 
 
 def robust_mean_batch(sample, maxiter=100, tol=1e-3, estep_tol=1e-3, estep_maxiter=100, theta=None, weights=None,
                       info=None, ws=None):
     """B robust means (robust_mean above; main.py:180-188) as ONE launch (rlvi_robust_mean_batch_f64): sample
     [B, n, d] -> (theta [B, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    theta, weights, info = _one_launch("rlvi_robust_mean_batch_f64", (sample,),
-                                       (int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _MEAN(True, (sample,), (maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def robust_pca_batch(sample, maxiter=100, tol=1e-2, theta_init=None, estep_tol=1e-3, estep_maxiter=100, theta=None,
                      weights=None, info=None, ws=None):
     """B robust PCAs (robust_pca above; main.py:489-494) as ONE launch (rlvi_robust_pca_batch_f64): sample [B, n, d],
     theta_init [d] for all of them (or None) -> (theta [B, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    if theta_init is not None:
-        _require_gpu(theta_init)
-        if not _fp64(theta_init, numel=d):
-            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
-    theta, weights, info = _one_launch(
-        "rlvi_robust_pca_batch_f64", (sample,),
-        (int(maxiter), float(tol), _ptr(theta_init), float(estep_tol), int(estep_maxiter)),
-        _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _PCA(True, (sample,), (maxiter, tol, theta_init, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def robust_covariance_batch(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3, estep_maxiter=100, theta=None,
@@ -764,12 +793,7 @@ def robust_covariance_batch(sample, n_eff, maxiter=100, tol=1e-2, estep_tol=1e-3
     """B robust covariances (robust_covariance above; main.py:539-544) as ONE launch
     (rlvi_robust_covariance_batch_f64): sample [B, n, d], one n_eff = n (1 - eps) for all of them -> (theta
     [B, d, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    theta, weights, info = _one_launch(
-        "rlvi_robust_covariance_batch_f64", (sample,),
-        (float(n_eff), int(maxiter), float(tol), float(estep_tol), int(estep_maxiter)),
-        _batch_outs(B, (theta, d * d), (weights, n)), info, ws)
-    return theta.view(B, d, d), weights.view(B, n), info.view(B, 4)
+    return _COVARIANCE(True, (sample,), (n_eff, maxiter, tol, estep_tol, estep_maxiter), (theta, weights), info, ws)
 
 
 def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, info=None, ws=None):
@@ -787,72 +811,44 @@ def update_weights_constrained(losses, n_eff, tol=1e-3, maxiter=100, out=None, i
 
 # ---- Robust Risk Minimization (standard-learning/rrm.py): the same kernels with the RRM weight rule; eps where the
 # entries above take n_eff, info = {outer, evaluations of the last root-find, evaluations | Jacobi sweeps in all, flag}.
-def _theta_init(theta_init, d):
-    if theta_init is not None:
-        _require_gpu(theta_init)
-        if not _fp64(theta_init, numel=d):
-            raise ValueError("theta_init must be a contiguous fp64 device tensor of d elements")
-    return _ptr(theta_init)
-
-
 def rrm_mean(sample, eps, maxiter=100, tol=1e-3, theta=None, weights=None, info=None, ws=None):
     """mean(sample, eps, maxiter, tol) of standard-learning/rrm.py:36-52 as ONE launch on device tensors
     (rlvi_rrm_mean_f64; no host synchronisation here).  Returns (theta [d], weights [n], info int32[4]); flag 1:
     nothing was written (data or a loss not finite, eps outside (0, 1), (1 - eps) n <= 1); flag 2: a root-find hit its
     200 evaluations (RLVI_ST_NOCONV in ws)."""
-    n, d = _sample_shape(sample)
-    return _one_launch("rlvi_rrm_mean_f64", (sample,), (float(eps), int(maxiter), float(tol)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _RRM_MEAN(False, (sample,), (eps, maxiter, tol), (theta, weights), info, ws)
 
 
 def rrm_pca(sample, eps, maxiter=100, tol=1e-2, theta_init=None, theta=None, weights=None, info=None, ws=None):
     """pca(sample, eps, maxiter, tol, theta_init) of standard-learning/rrm.py:94-107 as ONE launch on device tensors
     (rlvi_rrm_pca_f64); theta_init as for robust_pca.  Returns (theta [d], weights [n], info); info[2]: Jacobi sweeps
     in all."""
-    n, d = _sample_shape(sample)
-    return _one_launch("rlvi_rrm_pca_f64", (sample,),
-                       (float(eps), int(maxiter), float(tol), _theta_init(theta_init, d)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _RRM_PCA(False, (sample,), (eps, maxiter, tol, theta_init), (theta, weights), info, ws)
 
 
 def rrm_covariance(sample, eps, maxiter=100, tol=1e-2, theta=None, weights=None, info=None, ws=None):
     """covariance(sample, eps, maxiter, tol) of standard-learning/rrm.py:110-124 as ONE launch on device tensors
     (rlvi_rrm_covariance_f64).  Returns (theta [d, d], weights [n], info); flag 1 as for rrm_mean, and a pivot that
     is not safely positive."""
-    n, d = _sample_shape(sample)
-    theta, weights, info = _one_launch(
-        "rlvi_rrm_covariance_f64", (sample,), (float(eps), int(maxiter), float(tol)),
-        ((None if theta is None else theta.view(-1), d * d), (weights, n)), info, ws)
-    return theta.view(d, d), weights, info
+    return _RRM_COVARIANCE(False, (sample,), (eps, maxiter, tol), (theta, weights), info, ws)
 
 
 def rrm_mean_batch(sample, eps, maxiter=100, tol=1e-3, theta=None, weights=None, info=None, ws=None):
     """B calls of rrm_mean (the rrm.mean of main.py:180-188) as ONE launch (rlvi_rrm_mean_batch_f64): sample
     [B, n, d], one eps for all -> (theta [B, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    theta, weights, info = _one_launch("rlvi_rrm_mean_batch_f64", (sample,), (float(eps), int(maxiter), float(tol)),
-                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _RRM_MEAN(True, (sample,), (eps, maxiter, tol), (theta, weights), info, ws)
 
 
 def rrm_pca_batch(sample, eps, maxiter=100, tol=1e-2, theta_init=None, theta=None, weights=None, info=None, ws=None):
     """B calls of rrm_pca (main.py:489-494) as ONE launch (rlvi_rrm_pca_batch_f64): sample [B, n, d], one eps and one
     theta_init [d] (or None) for all -> (theta [B, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    theta, weights, info = _one_launch(
-        "rlvi_rrm_pca_batch_f64", (sample,), (float(eps), int(maxiter), float(tol), _theta_init(theta_init, d)),
-        _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _RRM_PCA(True, (sample,), (eps, maxiter, tol, theta_init), (theta, weights), info, ws)
 
 
 def rrm_covariance_batch(sample, eps, maxiter=100, tol=1e-2, theta=None, weights=None, info=None, ws=None):
     """B calls of rrm_covariance (main.py:539-544) as ONE launch (rlvi_rrm_covariance_batch_f64): sample [B, n, d],
     one eps for all -> (theta [B, d, d], weights [B, n], info int32[B, 4])."""
-    B, n, d = _batch_shape("sample", sample)
-    theta, weights, info = _one_launch(
-        "rlvi_rrm_covariance_batch_f64", (sample,), (float(eps), int(maxiter), float(tol)),
-        _batch_outs(B, (theta, d * d), (weights, n)), info, ws)
-    return theta.view(B, d, d), weights.view(B, n), info.view(B, 4)
+    return _RRM_COVARIANCE(True, (sample,), (eps, maxiter, tol), (theta, weights), info, ws)
 
 
 def rrm_update_weights(losses, eps, out=None, info=None, ws=None):
@@ -867,35 +863,20 @@ def rrm_update_weights(losses, eps, out=None, info=None, ws=None):
 
 
 # ---- the robust linear regressions of standard-learning/main.py:248-357 (robust_linreg.hip)
-def _linreg_inputs(X, y):
-    _require_gpu(X, y)
-    if not (_fp64(X, dims=2) and _fp64(y, numel=X.shape[0])):
-        raise ValueError("X [n, d] and y [n] must be contiguous fp64 device tensors")
-    return X.shape
-
-
 def rrm_linear_regression(X, y, eps, maxiter=100, tol=1e-3, out=None, info=None, ws=None):
     """linear_regression(X, y, eps, maxiter, tol) of standard-learning/rrm.py:55-73 as ONE launch on device tensors
     (rlvi_rrm_linear_regression_f64; no host synchronisation here).  out: (theta [d], weights [n]) to write into, or
     None.  Returns (theta, weights, info int32[4] = {outer iterations, evaluations of the last root-find, evaluations in
     all, flag}); flag 1 (a pivot not safely positive: compose rrm_update_weights / wls_solve instead) and flag 2 (a
     loss not finite): nothing was written; flag 3: a root-find hit its 200 evaluations (RLVI_ST_NOCONV in ws)."""
-    n, d = _linreg_inputs(X, y)
-    theta, weights = out if out is not None else (None, None)
-    return _one_launch("rlvi_rrm_linear_regression_f64", (X, y), (float(eps), int(maxiter), float(tol)),
-                       ((theta, d), (weights, n)), info, ws)
+    return _RRM_LINREG(False, (X, y), (eps, maxiter, tol), out or _NO_OUT, info, ws)
 
 
 def rrm_linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, out=None, info=None, ws=None):
     """B calls of rrm_linear_regression (the sweep of main.py:261-273) as ONE launch
     (rlvi_rrm_linear_regression_batch_f64): X [B, n, d], y [B, n], one eps for all -> (theta [B, d], weights [B, n],
     info int32[B, 4]); problem b has the bits of its single call."""
-    B, n, d = _batch_shape("X", X, y)
-    theta, weights = out if out is not None else (None, None)
-    theta, weights, info = _one_launch("rlvi_rrm_linear_regression_batch_f64", (X, y),
-                                       (float(eps), int(maxiter), float(tol)),
-                                       _batch_outs(B, (theta, d), (weights, n)), info, ws)
-    return theta.view(B, d), weights.view(B, n), info.view(B, 4)
+    return _RRM_LINREG(True, (X, y), (eps, maxiter, tol), out or _NO_OUT, info, ws)
 
 
 def huber_linear_regression(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=None, info=None, ws=None):
@@ -905,22 +886,15 @@ def huber_linear_regression(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=None, 
     int32[4] = {iterations, 0, 0, flag}); flag 1 (X^T X singular) and flag 2 (a scale not positive and finite, a theta
     not finite): nothing was written; flag 3: the cap was reached while the iteration still moved (RLVI_ST_NOCONV in
     ws, the last iterate written)."""
-    n, d = _linreg_inputs(X, y)
-    theta, scale = out if out is not None else (None, None)
-    return _one_launch("rlvi_huber_linear_regression_f64", (X, y), (float(c), float(sigma0), int(maxiter)),
-                       ((theta, d), (scale, 1)), info, ws)
+    return _HUBER_LINREG(False, (X, y), (c, sigma0, maxiter), out or _NO_OUT, info, ws)
 
 
 def huber_linear_regression_batch(X, y, c=0.7317, sigma0=1.0, maxiter=1000, out=None, info=None, ws=None):
     """B calls of huber_linear_regression (the sweep of main.py:261-273) as ONE launch
     (rlvi_huber_linear_regression_batch_f64): X [B, n, d], y [B, n], one c and sigma0 for all -> (theta [B, d], scale
     [B], info int32[B, 4]); problem b has the bits of its single call."""
-    B, n, d = _batch_shape("X", X, y)
-    theta, scale = out if out is not None else (None, None)
-    theta, scale, info = _one_launch("rlvi_huber_linear_regression_batch_f64", (X, y),
-                                     (float(c), float(sigma0), int(maxiter)),
-                                     _batch_outs(B, (theta, d), (scale, 1)), info, ws)
-    return theta.view(B, d), scale.view(B), info.view(B, 4)
+    theta, scale, info = _HUBER_LINREG(True, (X, y), (c, sigma0, maxiter), out or _NO_OUT, info, ws)
+    return theta, scale.view(-1), info
 
 
 # ---- RRM's logistic regression of standard-learning/main.py:361-470 (robust_logreg.hip)
@@ -931,22 +905,14 @@ def rrm_logistic_regression(X, y, eps, maxiter=100, tol=1e-2, C=100.0, out=None,
     last root-find, Newton steps in all, flag}); flag 1 (a label not 0 / 1, a value not finite): nothing was written;
     flag 2 (a fit at its Newton cap or without an acceptable step) and flag 3 (a root-find at its 200 evaluations):
     RLVI_ST_NOCONV in ws, the results written."""
-    n, d = _logistic_inputs(X, y)
-    theta, weights = out if out is not None else (None, None)
-    return _one_launch("rlvi_rrm_logistic_regression_f64", (X, y), (float(eps), int(maxiter), float(tol), float(C)),
-                       ((theta, d + 1), (weights, n)), info, ws)
+    return _RRM_LOGREG(False, (X, y), (eps, maxiter, tol, C), out or _NO_OUT, info, ws)
 
 
 def rrm_logistic_regression_batch(X, y, eps, maxiter=100, tol=1e-2, C=100.0, out=None, info=None, ws=None):
     """B calls of rrm_logistic_regression (the sweep of main.py:372-401) as ONE launch
     (rlvi_rrm_logistic_regression_batch_f64): X [B, n, d], y [B, n], one eps for all -> (theta [B, d + 1], weights
     [B, n], info int32[B, 4]); problem b has the bits of its single call."""
-    B, n, d = _batch_shape("X", X, y)
-    theta, weights = out if out is not None else (None, None)
-    theta, weights, info = _one_launch("rlvi_rrm_logistic_regression_batch_f64", (X, y),
-                                       (float(eps), int(maxiter), float(tol), float(C)),
-                                       _batch_outs(B, (theta, d + 1), (weights, n)), info, ws)
-    return theta.view(B, d + 1), weights.view(B, n), info.view(B, 4)
+    return _RRM_LOGREG(True, (X, y), (eps, maxiter, tol, C), out or _NO_OUT, info, ws)
 
 
 def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=100, out=None, losses=None,

@@ -27,6 +27,18 @@ from . import _lib, ops
 from . import standard as _std
 
 
+_NONFINITE = "array must not contain infs or NaNs"
+_LOGREG_FLAG1 = ("y must hold the class labels 0 and 1, and the fit must not meet numbers that are not finite (a design "
+                 "scaled beyond what fp64 resolves)")
+# what the kernels' flags raise (standard._raise_flags); flag 1 of the single linear_regression is its general path
+_UPDATE_FLAGS = {1: (ValueError, "{name}: a loss is not finite", False), 2: _std._CAP}
+_LINREG_FLAGS = {2: (ValueError, _NONFINITE, False), 3: _std._CAP}
+_LINREG_BATCH_FLAGS = {1: (ValueError, "{name}: a rank-deficient design (rrm.linear_regression takes its general path "
+                                       "there)", False),
+                       2: (ValueError, "{name}: " + _NONFINITE, False), 3: _std._CAP}
+_LOGREG_FLAGS = {1: (ValueError, "{name}: " + _LOGREG_FLAG1, False), 2: _std._CAP, 3: _std._CAP}
+
+
 def update_weights(losses, eps, *, return_info=False):
     '''Optimize sample weights for Robust Risk Minimization (reference rrm.py:12-33); n <= 4096.'''
     l = np.ascontiguousarray(losses, dtype=np.float64)
@@ -37,62 +49,54 @@ def update_weights(losses, eps, *, return_info=False):
     _std._rrm_eps("rrm.update_weights", eps, l.size)
     if l.size > 4096:
         raise _lib.RlviError(f"rrm.update_weights takes n <= 4096 losses in its one launch: got n = {l.size}")
-    dev = _std._dev()
-    ws = ops.workspace(dev, l.size, 0)
-    _, w, inf, _ = _std._one_launch_roundtrip(
-        dev, "rrm_update_weights", [(l, l.size)], 0, l.size,
-        lambda v, out: ops.rrm_update_weights(v[0], eps, out=out["weights"], info=out["info"], ws=ws))
-    inf = inf.copy()
-    if inf[3] == 1:
-        raise ValueError("rrm.update_weights: a loss is not finite")
-    if inf[3] == 2:
-        ws.raise_on_status("rrm.update_weights", mask=_lib.ST_NOCONV)
-    return (w.copy(), inf) if return_info else w.copy()
+    _, w, inf, _, ws = _std._one_launch_call("rrm.update_weights", ops.rrm_update_weights, [(l, None)], (eps,),
+                                             l.size, (0,), (l.size,), pair=True)
+    _std._raise_flags(ws, inf, return_info, "rrm.update_weights", _UPDATE_FLAGS)
+    return (w, inf) if return_info else w
 
 
 def mean(sample, eps, maxiter=100, tol=1e-3, *, return_info=False):
     """rrm.py:36-52 in ONE launch (2 <= n <= 4096, d <= 8, n d <= 16384: RlviError beyond)."""
-    return _std._moments_one_launch("mean", sample, maxiter, tol, return_info, eps=eps, rrm=True)
+    return _std._moments("mean", sample, maxiter, tol, return_info, eps=eps, rrm=True)
 
 
 def pca(sample, eps, maxiter=100, tol=1e-2, theta_init=None, *, return_info=False):
     """rrm.py:94-107 in ONE launch; theta_init replaces the first fit and is used as is (utils.py:81-88)."""
-    return _std._moments_one_launch("pca", sample, maxiter, tol, return_info, theta_init=theta_init, eps=eps, rrm=True)
+    return _std._moments("pca", sample, maxiter, tol, return_info, theta_init=theta_init, eps=eps, rrm=True)
 
 
 def covariance(sample, eps, maxiter=100, tol=1e-2, *, return_info=False):
     """rrm.py:110-124 in ONE launch; ValueError("Singular covariance matrix") as utils.py:99-100."""
-    return _std._moments_one_launch("covariance", sample, maxiter, tol, return_info, eps=eps, rrm=True)
+    return _std._moments("covariance", sample, maxiter, tol, return_info, eps=eps, rrm=True)
 
 
 def mean_batch(sample, eps, maxiter=100, tol=1e-3, *, return_info=False):
     """B calls of mean as ONE launch: sample [B, n, d] -> theta [B, d]; with return_info (theta, weights [B, n], info
     int32[B, 4]), a flagged problem's rows NaN and nothing raised."""
-    return _std._moments_batch("mean", sample, maxiter, tol, return_info, eps=eps, rrm=True)
+    return _std._moments("mean", sample, maxiter, tol, return_info, eps=eps, rrm=True, batch=True)
 
 
 def pca_batch(sample, eps, maxiter=100, tol=1e-2, theta_init=None, *, return_info=False):
     """B calls of pca as ONE launch: sample [B, n, d], ONE theta_init [d] for all problems -> theta [B, d]."""
-    return _std._moments_batch("pca", sample, maxiter, tol, return_info, theta_init=theta_init, eps=eps, rrm=True)
+    return _std._moments("pca", sample, maxiter, tol, return_info, theta_init=theta_init, eps=eps, rrm=True,
+                        batch=True)
 
 
 def covariance_batch(sample, eps, maxiter=100, tol=1e-2, *, return_info=False):
     """B calls of covariance as ONE launch: sample [B, n, d], ONE eps for all problems -> theta [B, d, d]."""
-    return _std._moments_batch("covariance", sample, maxiter, tol, return_info, eps=eps, rrm=True)
+    return _std._moments("covariance", sample, maxiter, tol, return_info, eps=eps, rrm=True, batch=True)
 
 
-def _linreg_inputs(what, X, y):
-    Xh = np.ascontiguousarray(X, dtype=np.float64)
-    yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-    if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
-        raise ValueError("X must be [n, d] and y [n]")
-    # what scipy's lstsq (check_finite) raises at rrm.py:58, before anything reaches the device
-    if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
-        raise ValueError("array must not contain infs or NaNs")
-    n, d = Xh.shape
+def _linreg_limits(what, n, d):
     if n == 0 or d == 0 or not ops.linear_regression_check(n, d):
         raise _lib.RlviError(f"{what} takes n <= 4096 samples and 1 <= d <= 31 features in its one launch: got "
                              f"n = {n}, d = {d}")
+
+
+def _linreg_inputs(what, X, y):
+    # (not finite: what scipy's lstsq (check_finite) raises at rrm.py:58)
+    Xh, yh, n, d = _std._design_inputs(X, y, nonfinite=_NONFINITE)
+    _linreg_limits(what, n, d)
     return Xh, yh, n, d
 
 
@@ -135,21 +139,14 @@ def linear_regression(X, y, eps, maxiter=100, tol=1e-3, *, return_info=False):
     then {its outer iterations, 0, 0, 1}."""
     Xh, yh, n, d = _linreg_inputs("rrm.linear_regression", X, y)
     _std._rrm_eps("rrm.linear_regression", eps, n)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, (Xd, yd) = _std._one_launch_roundtrip(
-        dev, "rrm_linreg", [(Xh, n * d), (yh, n)], d, n,
-        lambda v, out: ops.rrm_linear_regression(v[0].view(n, d), v[1], eps, maxiter=maxiter, tol=tol,
-                                                 out=(out["theta"], out["weights"]), info=out["info"], ws=ws))
-    inf = inf.copy()
+    theta, w, inf, (Xd, yd), ws = _std._one_launch_call("rrm.linear_regression", ops.rrm_linear_regression,
+                                                        [(Xh, (n, d)), (yh, None)], (eps, maxiter, tol), n, (d,), (n,),
+                                                        pair=True)
     if inf[3] == 1:
         th, wh, outer = _linear_regression_host_loop(Xd.view(n, d), yd, eps, maxiter, tol, ws)
         return (th, wh, np.array([outer, 0, 0, 1], np.int32)) if return_info else th
-    if inf[3] == 2:
-        raise ValueError("array must not contain infs or NaNs")
-    if inf[3] == 3:
-        ws.raise_on_status("rrm.linear_regression", mask=_lib.ST_NOCONV)
-    return (theta.copy(), w.copy(), inf) if return_info else theta.copy()
+    bad = _std._raise_flags(ws, inf, return_info, "rrm.linear_regression", _LINREG_FLAGS)
+    return _std._results(theta, w, inf, bad, return_info)
 
 
 def linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, *, return_info=False):
@@ -157,27 +154,14 @@ def linear_regression_batch(X, y, eps, maxiter=100, tol=1e-3, *, return_info=Fal
     all -> theta [B, d]; every problem has the bits of its single one-launch call.  A flagged problem raises what the
     single call's launch reports for it (flag 1: a rank-deficient design -- the batch form has no general path), naming
     the problem; with return_info (theta, weights [B, n], info int32[B, 4]) nothing is raised and its rows are NaN."""
-    Xh, yh, B, n, d = _std._batch_inputs("X", X, y, nonfinite="array must not contain infs or NaNs")
-    if n == 0 or d == 0 or not ops.linear_regression_check(n, d):
-        raise _lib.RlviError(f"rrm.linear_regression_batch takes n <= 4096 samples and 1 <= d <= 31 features in its one "
-                             f"launch: got n = {n}, d = {d}")
+    Xh, yh, B, n, d = _std._batch_inputs("X", X, y, nonfinite=_NONFINITE)
+    _linreg_limits("rrm.linear_regression_batch", n, d)
     _std._rrm_eps("rrm.linear_regression_batch", eps, n)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, _ = _std._one_launch_roundtrip(
-        dev, "rrm_linreg_batch", [(Xh, B * n * d), (yh, B * n)], d, n,
-        lambda v, out: ops.rrm_linear_regression_batch(v[0].view(B, n, d), v[1].view(B, n), eps, maxiter=maxiter,
-                                                       tol=tol, out=(out["theta"], out["weights"]), info=out["info"],
-                                                       ws=ws), batch=B)
-    inf = inf.copy().reshape(B, 4)
-    _linreg_batch_flags("rrm.linear_regression_batch", ws, inf, return_info,
-                        {1: "a rank-deficient design (rrm.linear_regression takes its general path there)",
-                         2: "array must not contain infs or NaNs"})
-    return _std._batch_results(theta, w, inf, B, (d,), n, return_info)
-
-
-_LOGREG_FLAG1 = ("y must hold the class labels 0 and 1, and the fit must not meet numbers that are not finite (a design "
-                 "scaled beyond what fp64 resolves)")
+    theta, w, inf, _, ws = _std._one_launch_call("rrm.linear_regression_batch", ops.rrm_linear_regression_batch,
+                                                 [(Xh, (B, n, d)), (yh, (B, n))], (eps, maxiter, tol), n, (d,), (n,),
+                                                 batch=B, pair=True)
+    bad = _std._raise_flags(ws, inf, return_info, "rrm.linear_regression_batch", _LINREG_BATCH_FLAGS, batch=True)
+    return _std._results(theta, w, inf, bad, return_info)
 
 
 def _logreg_checks(what, yh, n, d, eps, problems=False):
@@ -200,27 +184,14 @@ def logistic_regression(X, y, eps, maxiter=100, tol=1e-2, *, return_info=False):
     rule, so theta agrees with the reference's to liblinear's tolerance, not to the bit.  Reaching maxiter is silent,
     as in the reference.  return_info: (theta, weights [n], info int32[4] = {outer iterations, evaluations of the last
     root-find, Newton steps in all, flag})."""
-    Xh = np.ascontiguousarray(X, dtype=np.float64)
-    yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-    if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
-        raise ValueError("X must be [n, d] and y [n]")
-    # what sklearn's fit raises a ValueError for (utils.py:68), before anything reaches the device
-    if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
-        raise ValueError("Input contains NaN or infinity.")
-    n, d = Xh.shape
+    # (not finite: what sklearn's fit raises a ValueError for, utils.py:68)
+    Xh, yh, n, d = _std._design_inputs(X, y)
     _logreg_checks("rrm.logistic_regression", yh, n, d, eps)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, _ = _std._one_launch_roundtrip(
-        dev, "rrm_logreg", [(Xh, n * d), (yh, n)], d + 1, n,
-        lambda v, out: ops.rrm_logistic_regression(v[0].view(n, d), v[1], eps, maxiter=maxiter, tol=tol,
-                                                   out=(out["theta"], out["weights"]), info=out["info"], ws=ws))
-    inf = inf.copy()
-    if inf[3] == 1:
-        raise ValueError(f"rrm.logistic_regression: {_LOGREG_FLAG1}")
-    if inf[3] in (2, 3):
-        ws.raise_on_status("rrm.logistic_regression", mask=_lib.ST_NOCONV)
-    return (theta.copy(), w.copy(), inf) if return_info else theta.copy()
+    theta, w, inf, _, ws = _std._one_launch_call("rrm.logistic_regression", ops.rrm_logistic_regression,
+                                                 [(Xh, (n, d)), (yh, None)], (eps, maxiter, tol), n, (d + 1,), (n,),
+                                                 pair=True)
+    bad = _std._raise_flags(ws, inf, return_info, "rrm.logistic_regression", _LOGREG_FLAGS)
+    return _std._results(theta, w, inf, bad, return_info)
 
 
 def logistic_regression_batch(X, y, eps, maxiter=100, tol=1e-2, *, return_info=False):
@@ -230,35 +201,8 @@ def logistic_regression_batch(X, y, eps, maxiter=100, tol=1e-2, *, return_info=F
     info int32[B, 4]) nothing is raised and its rows are NaN."""
     Xh, yh, B, n, d = _std._batch_inputs("X", X, y)
     _logreg_checks("rrm.logistic_regression_batch", yh, n, d, eps, problems=True)
-    dev = _std._dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, _ = _std._one_launch_roundtrip(
-        dev, "rrm_logreg_batch", [(Xh, B * n * d), (yh, B * n)], d + 1, n,
-        lambda v, out: ops.rrm_logistic_regression_batch(v[0].view(B, n, d), v[1].view(B, n), eps, maxiter=maxiter,
-                                                         tol=tol, out=(out["theta"], out["weights"]),
-                                                         info=out["info"], ws=ws), batch=B)
-    inf = inf.copy().reshape(B, 4)
-    _linreg_batch_flags("rrm.logistic_regression_batch", ws, inf, return_info, {1: _LOGREG_FLAG1}, caps=(2, 3))
-    return _std._batch_results(theta, w, inf, B, (d + 1,), n, return_info)
-
-
-def _linreg_batch_flags(kind, ws, inf, return_info, value_errors, caps=(3,)):
-    """The convention of standard._batch_flags for kernels whose cap is flag 3 (`caps`: the flags that raise
-    RLVI_ST_NOCONV): with return_info nothing is raised (the caller blanks the flagged rows); otherwise the lowest
-    flagged problem raises -- ValueError with its text for the flags of `value_errors`, RlviError through the sticky
-    status for a cap flag.  The status word is cleared either way."""
-    flagged = np.flatnonzero(inf[:, 3] != 0)
-    if flagged.size == 0:
-        return
-    b = int(flagged[0])
-    flag = int(inf[b, 3])
-    if return_info or flag in value_errors:
-        if np.isin(inf[:, 3], caps).any():
-            ws.clear_status()
-        if return_info:
-            return
-        raise ValueError(f"{kind}: {value_errors[flag]} (problem {b})")
-    try:
-        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
-    except _lib.RlviError as e:
-        raise _lib.RlviError(f"{e} (problem {b})") from None
+    theta, w, inf, _, ws = _std._one_launch_call("rrm.logistic_regression_batch", ops.rrm_logistic_regression_batch,
+                                                 [(Xh, (B, n, d)), (yh, (B, n))], (eps, maxiter, tol), n, (d + 1,),
+                                                 (n,), batch=B, pair=True)
+    bad = _std._raise_flags(ws, inf, return_info, "rrm.logistic_regression_batch", _LOGREG_FLAGS, batch=True)
+    return _std._results(theta, w, inf, bad, return_info)

@@ -16,6 +16,10 @@ the host by default, as the reference has it, and runs as one launch of its own 
 with solver="newton" (logreg.hip).
 Host arrays cross PCIe once per call; use rlvi_amd.ops directly to keep data resident.
 """
+import collections
+import math
+import threading
+
 import numpy as np
 import torch
 
@@ -29,14 +33,20 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+# The staging set of a one-launch call: the pinned input buffer and its numpy view, the device input buffer and the
+# device views of its parts, the pinned and the device output buffer, the device views {theta, weights, info} of the
+# latter and the numpy views (theta, weights, info) of the former.
+_OneLaunchSet = collections.namedtuple("_OneLaunchSet", "h_in host d_in views h_out d_out outs res")
+
+
 class _Staging:
     """Pinned host buffers for the numpy-in / numpy-out calls: one set per (thread, device, tag, sizes), least
     recently used evicted beyond 32 sets.  Keyed by the thread as well: the buffers are written, copied
-    asynchronously and read back around ONE host wait, so two threads must never share a set."""
+    asynchronously and read back around ONE host wait, so two threads must never share a set.  A one-launch call's
+    set (one_launch) is keyed by how its two buffers are split and keeps the views of the parts with them: a call
+    slices nothing."""
 
     def __init__(self, cap=32):
-        import collections
-        import threading
         self._lock = threading.Lock()
         self._sets = collections.OrderedDict()
         self._cap = cap
@@ -44,8 +54,7 @@ class _Staging:
     def get(self, dev, tag, sizes, dtype=torch.float64, device_side=False):
         """(h_0, h_1, ...) pinned host buffers of the given lengths; device_side: followed by device buffers of the
         same lengths (kept with the set: a call then allocates nothing)."""
-        import threading
-        key = (threading.get_ident(), dev.index, tag, tuple(int(x) for x in sizes), dtype, device_side)
+        key = (threading.get_ident(), dev.index, tag, tuple(map(int, sizes)), dtype, device_side)
         with self._lock:
             st = self._sets.get(key)
             if st is not None:
@@ -54,6 +63,29 @@ class _Staging:
         st = tuple(torch.empty(max(int(x), 1), dtype=dtype).pin_memory() for x in sizes)
         if device_side:
             st = st + tuple(torch.empty(max(int(x), 1), dtype=dtype, device=dev) for x in sizes)
+        return self._keep(key, st)
+
+    def one_launch(self, dev, tag, lengths, nt, n, batch):
+        """The set of a one-launch call (_OneLaunchSet) -- inputs of the given lengths in one buffer, {theta [nt],
+        weights [n], info int32[4 batch]} in another -- with its views, made once."""
+        key = (threading.get_ident(), dev.index, tag, lengths, nt, n, batch)
+        with self._lock:
+            st = self._sets.get(key)
+            if st is not None:
+                self._sets.move_to_end(key)
+                return st
+        sizes = (max(sum(lengths), 1), nt + n + 2 * batch)
+        h_in, h_out = (torch.empty(k, dtype=torch.float64).pin_memory() for k in sizes)
+        d_in, d_out = (torch.empty(k, dtype=torch.float64, device=dev) for k in sizes)
+        offs = [sum(lengths[:i]) for i in range(len(lengths))]
+        res = h_out.numpy()
+        # info: 4 x int32 per problem behind theta and the weights
+        return self._keep(key, _OneLaunchSet(
+            h_in, h_in.numpy(), d_in, tuple(d_in[o:o + k] for o, k in zip(offs, lengths)), h_out, d_out,
+            dict(theta=d_out[:nt], weights=d_out[nt:nt + n], info=d_out[nt + n:].view(torch.int32)),
+            (res[:nt], res[nt:nt + n], res[nt + n:].view(np.int32))))
+
+    def _keep(self, key, st):
         with self._lock:
             self._sets[key] = st
             while len(self._sets) > self._cap:
@@ -89,22 +121,84 @@ def _one_launch_roundtrip(dev, tag, parts, nt, n, launch, batch=1):
     weights [n], info int32[4])), ONE pinned copy of {theta, weights, info} back and the one host wait of the call.
     Returns (theta, weights, info) as views of the pinned result -- copy what is handed out -- and the device views.
     batch = B: the batch forms, whose theta, weights and info are B rows of nt, n and 4 (returned flat)."""
-    total = sum(length for _, length in parts)
-    nt, n = batch * nt, batch * n
-    h_in, h_out, d_in, d_out = _STAGE.get(dev, tag, (total, nt + n + 2 * batch), device_side=True)
-    views, off = [], 0
+    st = _STAGE.one_launch(dev, tag, tuple([int(length) for _, length in parts]), batch * nt, batch * n, batch)
+    off = 0
     for a, length in parts:
         if a is not None:
-            h_in.numpy()[off:off + length] = a.reshape(-1)
-        views.append(d_in[off:off + length])
+            st.host[off:off + length] = a.reshape(-1)
         off += length
-    d_in.copy_(h_in, non_blocking=True)
-    # info: 4 x int32 behind theta and the weights
-    launch(views, dict(theta=d_out[:nt], weights=d_out[nt:nt + n], info=d_out[nt + n:].view(torch.int32)))
-    h_out.copy_(d_out, non_blocking=True)
+    st.d_in.copy_(st.h_in, non_blocking=True)
+    launch(st.views, dict(st.outs))                     # (a copy: launch may add to it)
+    st.h_out.copy_(st.d_out, non_blocking=True)
     torch.cuda.current_stream(dev).synchronize()
-    res = h_out.numpy()
-    return res[:nt], res[nt:nt + n], res[nt + n:].view(np.int32), views
+    return (*st.res, st.views)
+
+
+def _one_launch_call(name, fn, inputs, args, n, theta_row, second_row, batch=None, pair=False, theta_init=None):
+    """What every numpy-level one-launch estimator does around its launch.  fn: the rlvi_amd.ops callee (the batch
+    form's with batch = B); inputs: [(host array, shape of its device view -- None: flat)], its leading arguments;
+    args: the scalars after them; theta_init: a host vector staged behind the inputs and passed by that keyword; n: the
+    samples of a problem; theta_row, second_row: the shape of one problem's theta and of its weights (or scale).  The
+    staged output views go to fn as theta=, weights=, info= -- pair: as out=(theta, weights), info= (a theta_row of no
+    elements: out=weights) -- with the workspace.  One staging set per `name`, which is the estimator and its form.
+    Returns owned copies of theta, the second output and info, [B, ...] with batch = B and unbatched without, then the
+    flat device views of the staged arrays and the workspace."""
+    dev = _dev()
+    ws = ops.workspace(dev, n, 0)
+    nt, ns = math.prod(theta_row), math.prod(second_row)
+    parts = [(a, a.size) for a, _ in inputs]
+    if theta_init is not None:
+        parts.append((theta_init, theta_init.size))
+
+    def launch(views, out):
+        kw = out
+        if pair:
+            kw = dict(out=(out["theta"], out["weights"]) if nt else out["weights"], info=out["info"])
+        if theta_init is not None:
+            kw["theta_init"] = views[-1]
+        fn(*[t if shape is None else t.view(shape) for t, (_, shape) in zip(views, inputs)], *args, ws=ws, **kw)
+    theta, second, info, views = _one_launch_roundtrip(dev, name, parts, nt, ns, launch, batch=batch or 1)
+    theta, second, info = theta.copy(), second.copy(), info.copy()
+    if batch is not None:
+        lead = (batch,)
+        theta, second, info = theta.reshape(lead + theta_row), second.reshape(lead + second_row), info.reshape(batch, 4)
+    elif len(theta_row) != 1 or len(second_row) != 1:                # (a covariance matrix, Huber's scalar scale)
+        theta, second = theta.reshape(theta_row), second.reshape(second_row)
+    return theta, second, info, views, ws
+
+
+# What a kernel's flag (info[..., 3]) means to the caller, per estimator: {flag: (exception class, message, cap)}.  The
+# message is formatted with the estimator's name (and what else _raise_flags is given); cap: the kernel also raised
+# RLVI_ST_NOCONV in the workspace's sticky status word.  _CAP: a cap reported through that word.
+_CAP = (None, None, True)
+
+
+def _raise_flags(ws, info, return_info, name, table, batch=False, **fmt):
+    """The one reading of info[..., 3].  The lowest flagged problem raises what `table` has for its flag -- a batch
+    naming the problem; a single form is a batch of one that does not, and raises with return_info as well.  With
+    return_info a batch raises nothing: the caller blanks the flagged rows, info says which.  A _CAP flag raises
+    through ws.raise_on_status, which clears the sticky status word; on every other way out the word is cleared here
+    if any problem holds a cap flag.  Returns the mask of the flagged problems."""
+    flags = info.reshape(-1, 4)[:, 3]
+    bad = flags != 0
+    if not bad.any():
+        return bad
+    b = int(np.argmax(bad))
+    where = f" (problem {b})" if batch else ""
+    # (a flag the table does not know, which no kernel writes today, is taken for a cap: never silent)
+    cls, text, _ = table.get(int(flags[b]), _CAP)
+    quiet = batch and return_info
+    if quiet or cls is not None:
+        if any(table.get(int(f), _CAP)[2] for f in flags[bad]):
+            ws.clear_status()
+        if quiet:
+            return bad
+        raise cls(text.format(name=name, **fmt) + where)
+    try:
+        ws.raise_on_status(name, mask=_lib.ST_NOCONV)
+    except _lib.RlviError as e:
+        raise _lib.RlviError(f"{e}{where}") from None
+    return bad
 
 
 def update_weights(losses, tol=1e-3, maxiter=100):
@@ -151,15 +245,12 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, return_info=False):
     the stop test ||theta - prev|| / ||prev|| <= tol all on the device) between one pinned H2D copy of [X | y]
     and one pinned D2H copy of {theta, weights, info}; the host waits once.  Beyond that, or when the launch
     reports a rank-deficient design: the general path."""
-    dev = _dev()
     Xh = np.ascontiguousarray(X, dtype=np.float64)
     yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
     n, d = Xh.shape
-    ws = ops.workspace(dev, n, 0)
     if n > 0 and d > 0 and ops.linear_regression_check(n, d):
-        theta, w, inf, (Xd, yd) = _one_launch_roundtrip(
-            dev, "linreg", [(Xh, n * d), (yh, n)], d, n,
-            lambda v, out: ops.linear_regression(v[0].view(n, d), v[1], maxiter=maxiter, tol=tol, ws=ws, **out))
+        theta, w, inf, (Xd, yd), ws = _one_launch_call("linear_regression", ops.linear_regression,
+                                                       [(Xh, (n, d)), (yh, None)], (maxiter, tol), n, (d,), (n,))
         if inf[3] == 0:
             if not np.isfinite(theta).all():
                 # a NaN or inf in y alone passes the pivot test (which looks at X^T W X) and, with maxiter = 0, no
@@ -167,10 +258,12 @@ def linear_regression(X, y, maxiter=100, tol=1e-3, return_info=False):
                 ws.clear_status()
                 raise ValueError("array must not contain infs or NaNs")
             if return_info:
-                return theta.copy(), w.copy(), int(inf[0])
-            return theta.copy()
+                return theta, w, int(inf[0])
+            return theta
         Xd = Xd.view(n, d)
     else:
+        dev = _dev()
+        ws = ops.workspace(dev, n, 0)
         Xd, yd = torch.from_numpy(Xh).to(dev), torch.from_numpy(yh).to(dev)
     theta, w, outer = _linear_regression_host_loop(Xd, yd, maxiter, tol)
     th = theta.cpu().numpy()
@@ -202,17 +295,29 @@ def _sklearn_log_reg(X_host, y_host, X_dev, w_dev, reg_coeff=1e2):
     return theta, losses
 
 
-def _logistic_regression_newton(X, y, maxiter, tol, return_info):
-    """solver="newton": one pinned H2D copy of [X | y], ONE launch (rlvi_logistic_regression_f64), one pinned D2H
-    copy of {theta, weights, info}, one host wait."""
+def _design_inputs(X, y, nonfinite="Input contains NaN or infinity."):
+    """X [n, d] and y [n] as contiguous fp64 host arrays, all finite (what is not raises `nonfinite`), before anything
+    reaches the device: the single forms' _batch_inputs.  Returns (X, y, n, d)."""
     Xh = np.ascontiguousarray(X, dtype=np.float64)
     yh = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
     if Xh.ndim != 2 or yh.shape[0] != Xh.shape[0]:
         raise ValueError("X must be [n, d] and y [n]")
-    n, d = Xh.shape
-    # what sklearn's fit raises a ValueError for, before anything reaches the device
     if not (np.isfinite(Xh).all() and np.isfinite(yh).all()):
-        raise ValueError("Input contains NaN or infinity.")
+        raise ValueError(nonfinite)
+    return Xh, yh, *Xh.shape
+
+
+_LOGREG_FLAGS = {1: (ValueError, "logistic_regression: the fit met numbers that are not finite, or a pivot of its "
+                                 "Newton system that is not safely positive (a design scaled beyond what fp64 "
+                                 "resolves)", False),
+                 2: _CAP}
+
+
+def _logistic_regression_newton(X, y, maxiter, tol, return_info):
+    """solver="newton": one pinned H2D copy of [X | y], ONE launch (rlvi_logistic_regression_f64), one pinned D2H
+    copy of {theta, weights, info}, one host wait."""
+    # what sklearn's fit raises a ValueError for, before anything reaches the device
+    Xh, yh, n, d = _design_inputs(X, y)
     if not np.isin(yh, (0.0, 1.0)).all():
         raise ValueError("y must hold the class labels 0 and 1")
     if n == 0 or yh.min() == yh.max():
@@ -220,20 +325,12 @@ def _logistic_regression_newton(X, y, maxiter, tol, return_info):
     if d == 0 or not ops.logistic_regression_check(n, d):
         raise _lib.RlviError(f"logistic_regression(solver='newton') takes n <= 4096 samples and 1 <= d <= 30 features "
                              f"in its one launch: got n = {n}, d = {d} (solver='liblinear' has no such limit)")
-    dev = _dev()
-    ws = ops.workspace(dev, n, 0)
-    D = d + 1
-    theta, w, inf, _ = _one_launch_roundtrip(
-        dev, "logreg", [(Xh, n * d), (yh, n)], D, n,
-        lambda v, out: ops.logistic_regression(v[0].view(n, d), v[1], maxiter=maxiter, tol=tol, ws=ws, **out))
-    if inf[3] == 1:
-        raise ValueError("logistic_regression: the fit met numbers that are not finite, or a pivot of its Newton "
-                         "system that is not safely positive (a design scaled beyond what fp64 resolves)")
-    if inf[3] == 2:
-        ws.raise_on_status("logistic_regression", mask=_lib.ST_NOCONV)
+    theta, w, inf, _, ws = _one_launch_call("logistic_regression", ops.logistic_regression,
+                                            [(Xh, (n, d)), (yh, None)], (maxiter, tol), n, (d + 1,), (n,))
+    _raise_flags(ws, inf, return_info, "logistic_regression", _LOGREG_FLAGS)
     if return_info:
-        return theta.copy(), w.copy(), int(inf[0])
-    return theta.copy()
+        return theta, w, int(inf[0])
+    return theta
 
 
 def logistic_regression(X, y, maxiter=100, tol=1e-2, *, solver="liblinear", return_info=False):
@@ -292,60 +389,66 @@ def _rrm_eps(what, eps, n):
         raise ValueError(f"{what} needs 0 < eps < 1 and (1 - eps) n > 1: got eps = {eps}, n = {n}")
 
 
-def _moments_one_launch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None, rrm=False):
-    """one_launch=True of mean / pca / covariance: one pinned H2D copy of the sample (and theta_init), ONE launch
-    (rlvi_robust_mean_f64 / _pca_f64 / _covariance_f64), one pinned D2H copy of {theta, weights, info}, one host
-    wait.  rrm: the estimators of rlvi_amd/rrm.py on the same path (rlvi_rrm_mean_f64 / _pca_f64 / _covariance_f64)."""
-    xh = np.ascontiguousarray(sample, dtype=np.float64)
-    if xh.ndim != 2:
-        raise ValueError("sample must be [n, d]")
-    n, d = xh.shape
+_VARIANCE_FLAGS = {1: (ValueError, "{kind}: the estimator met numbers that are not finite, or a variance that is not "
+                                   "safely positive", False),
+                   2: _CAP}
+_SINGULAR_FLAGS = {1: (ValueError, "Singular covariance matrix", False), 2: _CAP}          # utils.py:99-100
+
+
+def _rlvi_args(n, eps, maxiter, tol):
+    return maxiter, tol
+
+
+def _rrm_args(n, eps, maxiter, tol):
+    return eps, maxiter, tol
+
+
+# (kind, rrm) -> the rlvi_amd.ops callee, its scalars of (n, eps, maxiter, tol), theta's shape of d, its flags
+_MOMENTS = {
+    ("mean", False): ("robust_mean", _rlvi_args, lambda d: (d,), _VARIANCE_FLAGS),
+    ("pca", False): ("robust_pca", _rlvi_args, lambda d: (d,), _VARIANCE_FLAGS),
+    ("covariance", False): ("robust_covariance", lambda n, eps, maxiter, tol: (n * (1 - eps), maxiter, tol),
+                            lambda d: (d, d), _SINGULAR_FLAGS),
+    ("mean", True): ("rrm_mean", _rrm_args, lambda d: (d,), _VARIANCE_FLAGS),
+    ("pca", True): ("rrm_pca", _rrm_args, lambda d: (d,), _VARIANCE_FLAGS),
+    ("covariance", True): ("rrm_covariance", _rrm_args, lambda d: (d, d), _SINGULAR_FLAGS),
+}
+
+
+def _moments(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None, rrm=False, batch=False):
+    """one_launch=True of mean / pca / covariance (rlvi_robust_mean_f64 / _pca_f64 / _covariance_f64), rrm: the
+    estimators of rlvi_amd/rrm.py on the same path (rlvi_rrm_*_f64), batch: their batch forms on [B, n, d]: one pinned
+    H2D copy of the sample (and theta_init), ONE launch, one pinned D2H copy of {theta, weights, info}, one host
+    wait."""
+    name = ("rrm." if rrm else "") + kind + ("_batch" if batch else "")
+    shown = name if rrm or batch else f"{kind}(one_launch=True)"
+    if batch:
+        xh, _, B, n, d = _batch_inputs("sample", sample)
+    else:
+        xh = np.ascontiguousarray(sample, dtype=np.float64)
+        if xh.ndim != 2:
+            raise ValueError("sample must be [n, d]")
+        B, (n, d) = None, xh.shape
     init = None if theta_init is None else np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
     if init is not None and init.shape[0] != d:
-        raise ValueError("theta_init must have the sample's d elements")
-    # before anything reaches the device
-    if not np.isfinite(xh).all() or (init is not None and not np.isfinite(init).all()):
+        raise ValueError("theta_init must have the " + ("samples'" if batch else "sample's") + " d elements")
+    # before anything reaches the device (_batch_inputs has looked at the samples of a batch)
+    if not ((batch or np.isfinite(xh).all()) and (init is None or np.isfinite(init).all())):
         raise ValueError("Input contains NaN or infinity.")
     if rrm:
-        _rrm_eps(f"rrm.{kind}", eps, n)
-    elif kind == "covariance" and not 0.0 < eps < 1.0:
-        raise ValueError(f"covariance(one_launch=True) needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
+        _rrm_eps(name, eps, n)
+    elif eps is not None and not 0.0 < eps < 1.0:                    # (eps: the covariance alone)
+        raise ValueError(f"{shown} needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
     if n == 0 or d == 0 or not ops.moments_check(n, d):
-        if rrm:
-            raise _lib.RlviError(f"rrm.{kind} takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with n d <= 16384 "
-                                 f"in its one launch: got n = {n}, d = {d}")
-        raise _lib.RlviError(f"{kind}(one_launch=True) takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with "
-                             f"n d <= 16384 in its one launch: got n = {n}, d = {d} (one_launch=False has no such "
-                             f"limit)")
-    dev = _dev()
-    ws = ops.workspace(dev, n, 0)
-    nt = d * d if kind == "covariance" else d
-
-    def launch(v, out):
-        x_dev = v[0].view(n, d)
-        if rrm:
-            init_kw = dict(theta_init=None if init is None else v[1]) if kind == "pca" else {}
-            getattr(ops, "rrm_" + kind)(x_dev, eps, maxiter=maxiter, tol=tol, ws=ws, **init_kw, **out)
-        elif kind == "mean":
-            ops.robust_mean(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
-        elif kind == "pca":
-            ops.robust_pca(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws, **out)
-        else:
-            ops.robust_covariance(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
-    theta, w, inf, _ = _one_launch_roundtrip(dev, ("rrm_" if rrm else "moments_") + kind, [(xh, n * d), (init, d)], nt,
-                                             n, launch)
-    inf = inf.copy()
-    if inf[3] == 1:
-        if kind == "covariance":
-            raise ValueError("Singular covariance matrix")   # utils.py:99-100
-        raise ValueError(f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely "
-                         f"positive")
-    if inf[3] == 2:
-        ws.raise_on_status(("rrm." if rrm else "") + kind, mask=_lib.ST_NOCONV)
-    theta = theta.copy().reshape((d, d) if kind == "covariance" else (d,))
-    if return_info:
-        return theta, w.copy(), inf
-    return theta
+        raise _lib.RlviError(f"{shown} takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions with n d <= 16384 in its "
+                             f"one launch: got n = {n}, d = {d}"
+                             + ("" if rrm or batch else " (one_launch=False has no such limit)"))
+    stem, scalars, shape, flags = _MOMENTS[kind, rrm]
+    theta, w, inf, _, ws = _one_launch_call(
+        name, getattr(ops, stem + "_batch" if batch else stem), [(xh, (n, d) if B is None else (B, n, d))],
+        scalars(n, eps, maxiter, tol), n, shape(d), (n,), batch=B, theta_init=init)
+    bad = _raise_flags(ws, inf, return_info, name, flags, batch, kind=kind)
+    return _results(theta, w, inf, bad, return_info)
 
 
 def _host_loop_only(one_launch, return_info):
@@ -359,7 +462,7 @@ def mean(sample, maxiter=100, tol=1e-3, *, one_launch=False, return_info=False):
     iterations, inner iterations of the last E-step, inner iterations in all, flag})."""
     _host_loop_only(one_launch, return_info)
     if one_launch:
-        return _moments_one_launch("mean", sample, maxiter, tol, return_info)
+        return _moments("mean", sample, maxiter, tol, return_info)
     sample = np.asarray(sample, np.float64)
     w = np.ones(sample.shape[0])
     theta = w @ sample / np.sum(w)
@@ -392,7 +495,7 @@ def pca(sample, maxiter=100, tol=1e-2, theta_init=None, *, one_launch=False, ret
     all)."""
     _host_loop_only(one_launch, return_info)
     if one_launch:
-        return _moments_one_launch("pca", sample, maxiter, tol, return_info, theta_init=theta_init)
+        return _moments("pca", sample, maxiter, tol, return_info, theta_init=theta_init)
     sample = np.asarray(sample, np.float64)
     w = np.ones(sample.shape[0])
     if theta_init is None:
@@ -428,7 +531,7 @@ def covariance(sample, eps, maxiter=100, tol=1e-2, *, one_launch=False, return_i
     the bit."""
     _host_loop_only(one_launch, return_info)
     if one_launch:
-        return _moments_one_launch("covariance", sample, maxiter, tol, return_info, eps=eps)
+        return _moments("covariance", sample, maxiter, tol, return_info, eps=eps)
     sample = np.asarray(sample, np.float64)
     n = sample.shape[0]
     n_eff = n * (1 - eps)
@@ -469,34 +572,15 @@ def _batch_inputs(what, X, y=None, nonfinite="Input contains NaN or infinity."):
     return Xh, yh, B, n, d
 
 
-def _batch_flags(kind, ws, inf, return_info, flag1):
-    """The per-problem flags of a batch: what the single call raises for the lowest flagged problem, naming it -- or,
-    with return_info, nothing (the caller blanks the flagged rows; info says which).  The sticky NOCONV word that a
-    flag 2 raised is cleared either way."""
-    flagged = np.flatnonzero(inf[:, 3] != 0)
-    if flagged.size == 0:
-        return
-    b = int(flagged[0])
-    if return_info or inf[b, 3] == 1:
-        if (inf[:, 3] == 2).any():
-            ws.clear_status()
-        if return_info:
-            return
-        raise ValueError(f"{flag1} (problem {b})")
-    try:
-        ws.raise_on_status(kind, mask=_lib.ST_NOCONV)
-    except _lib.RlviError as e:
-        raise _lib.RlviError(f"{e} (problem {b})") from None
-
-
-def _batch_results(theta, w, inf, B, theta_shape, n, return_info):
-    theta, w = theta.copy().reshape((B,) + theta_shape), w.copy().reshape(B, n)
+def _results(theta, second, info, bad, return_info):
+    """What a call hands out after _raise_flags: theta -- with return_info (theta, second, info), the rows of a
+    batch's flagged problems (`bad`) NaN."""
     if not return_info:
         return theta
-    bad = inf[:, 3] != 0
-    theta[bad] = np.nan
-    w[bad] = np.nan
-    return theta, w, inf
+    if info.ndim == 2:
+        theta[bad] = np.nan
+        second[bad] = np.nan
+    return theta, second, info
 
 
 def linear_regression_batch(X, y, maxiter=100, tol=1e-3, return_info=False):
@@ -509,13 +593,9 @@ def linear_regression_batch(X, y, maxiter=100, tol=1e-3, return_info=False):
     if B == 0 or n == 0 or d == 0 or not ops.linear_regression_check(n, d):
         raise _lib.RlviError(f"linear_regression_batch takes B >= 1 problems of n <= 4096 samples and 1 <= d <= 31 "
                              f"features in its one launch: got B = {B}, n = {n}, d = {d}")
-    dev = _dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, (Xd, yd) = _one_launch_roundtrip(
-        dev, "linreg_batch", [(Xh, B * n * d), (yh, B * n)], d, n,
-        lambda v, out: ops.linear_regression_batch(v[0].view(B, n, d), v[1].view(B, n), maxiter=maxiter, tol=tol,
-                                                   ws=ws, **out), batch=B)
-    theta, w, inf = theta.copy().reshape(B, d), w.copy().reshape(B, n), inf.copy().reshape(B, 4)
+    theta, w, inf, (Xd, yd), ws = _one_launch_call("linear_regression_batch", ops.linear_regression_batch,
+                                                   [(Xh, (B, n, d)), (yh, (B, n))], (maxiter, tol), n, (d,), (n,),
+                                                   batch=B)
     for b in np.flatnonzero(inf[:, 3] == 1):
         th_b, w_b, outer = _linear_regression_host_loop(Xd.view(B, n, d)[b], yd.view(B, n)[b], maxiter, tol)
         theta[b] = th_b.cpu().numpy()
@@ -544,73 +624,25 @@ def logistic_regression_batch(X, y, maxiter=100, tol=1e-2, return_info=False):
     if d == 0 or not ops.logistic_regression_check(n, d):
         raise _lib.RlviError(f"logistic_regression_batch takes n <= 4096 samples and 1 <= d <= 30 features in its one "
                              f"launch: got n = {n}, d = {d}")
-    dev = _dev()
-    ws = ops.workspace(dev, n, 0)
-    theta, w, inf, _ = _one_launch_roundtrip(
-        dev, "logreg_batch", [(Xh, B * n * d), (yh, B * n)], d + 1, n,
-        lambda v, out: ops.logistic_regression_batch(v[0].view(B, n, d), v[1].view(B, n), maxiter=maxiter, tol=tol,
-                                                     ws=ws, **out), batch=B)
-    inf = inf.copy().reshape(B, 4)
-    _batch_flags("logistic_regression_batch", ws, inf, return_info,
-                 "logistic_regression: the fit met numbers that are not finite, or a pivot of its Newton system that "
-                 "is not safely positive (a design scaled beyond what fp64 resolves)")
-    return _batch_results(theta, w, inf, B, (d + 1,), n, return_info)
-
-
-def _moments_batch(kind, sample, maxiter, tol, return_info, theta_init=None, eps=None, rrm=False):
-    """mean_batch / pca_batch / covariance_batch; rrm: those of rlvi_amd/rrm.py (rlvi_rrm_*_batch_f64)"""
-    xh, _, B, n, d = _batch_inputs("sample", sample)
-    init = None if theta_init is None else np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
-    if init is not None and init.shape[0] != d:
-        raise ValueError("theta_init must have the samples' d elements")
-    if init is not None and not np.isfinite(init).all():
-        raise ValueError("Input contains NaN or infinity.")
-    if rrm:
-        _rrm_eps(f"rrm.{kind}_batch", eps, n)
-    elif kind == "covariance" and not 0.0 < eps < 1.0:
-        raise ValueError(f"covariance_batch needs 0 < eps < 1 (n_eff = n (1 - eps) inside (0, n)): got {eps}")
-    if n == 0 or d == 0 or not ops.moments_check(n, d):
-        raise _lib.RlviError(f"{'rrm.' if rrm else ''}{kind}_batch takes 2 <= n <= 4096 samples of 1 <= d <= 8 dimensions "
-                             f"with n d <= 16384 in its one launch: got n = {n}, d = {d}")
-    dev = _dev()
-    ws = ops.workspace(dev, n, 0)
-    shape = (d, d) if kind == "covariance" else (d,)
-
-    def launch(v, out):
-        x_dev = v[0].view(B, n, d)
-        if rrm:
-            init_kw = dict(theta_init=None if init is None else v[1]) if kind == "pca" else {}
-            getattr(ops, f"rrm_{kind}_batch")(x_dev, eps, maxiter=maxiter, tol=tol, ws=ws, **init_kw, **out)
-        elif kind == "mean":
-            ops.robust_mean_batch(x_dev, maxiter=maxiter, tol=tol, ws=ws, **out)
-        elif kind == "pca":
-            ops.robust_pca_batch(x_dev, maxiter=maxiter, tol=tol, theta_init=None if init is None else v[1], ws=ws,
-                                 **out)
-        else:
-            ops.robust_covariance_batch(x_dev, n * (1 - eps), maxiter=maxiter, tol=tol, ws=ws, **out)
-    theta, w, inf, _ = _one_launch_roundtrip(dev, ("rrm_batch_" if rrm else "moments_batch_") + kind,
-                                             [(xh, B * n * d), (init, d)],
-                                             int(np.prod(shape)), n, launch, batch=B)
-    inf = inf.copy().reshape(B, 4)
-    _batch_flags(("rrm." if rrm else "") + kind + "_batch", ws, inf, return_info,
-                 "Singular covariance matrix" if kind == "covariance" else
-                 f"{kind}: the estimator met numbers that are not finite, or a variance that is not safely positive")
-    return _batch_results(theta, w, inf, B, shape, n, return_info)
+    theta, w, inf, _, ws = _one_launch_call("logistic_regression_batch", ops.logistic_regression_batch,
+                                            [(Xh, (B, n, d)), (yh, (B, n))], (maxiter, tol), n, (d + 1,), (n,), batch=B)
+    bad = _raise_flags(ws, inf, return_info, "logistic_regression_batch", _LOGREG_FLAGS, batch=True)
+    return _results(theta, w, inf, bad, return_info)
 
 
 def mean_batch(sample, maxiter=100, tol=1e-3, return_info=False):
     """B calls of mean(one_launch=True) (main.py:180-188) as ONE launch: sample [B, n, d] -> theta [B, d]; limits and
     return_info as for mean, info int32[B, 4]; with return_info a flagged problem's rows are NaN, nothing is raised."""
-    return _moments_batch("mean", sample, maxiter, tol, return_info)
+    return _moments("mean", sample, maxiter, tol, return_info, batch=True)
 
 
 def pca_batch(sample, maxiter=100, tol=1e-2, theta_init=None, return_info=False):
     """B calls of pca(one_launch=True) (main.py:489-494) as ONE launch: sample [B, n, d], ONE theta_init [d] for all
     problems (as in the reference's loop) -> theta [B, d]."""
-    return _moments_batch("pca", sample, maxiter, tol, return_info, theta_init=theta_init)
+    return _moments("pca", sample, maxiter, tol, return_info, theta_init=theta_init, batch=True)
 
 
 def covariance_batch(sample, eps, maxiter=100, tol=1e-2, return_info=False):
     """B calls of covariance(one_launch=True) (main.py:539-544) as ONE launch: sample [B, n, d], ONE eps for all
     problems -> theta [B, d, d]."""
-    return _moments_batch("covariance", sample, eps=eps, maxiter=maxiter, tol=tol, return_info=return_info)
+    return _moments("covariance", sample, maxiter, tol, return_info, eps=eps, batch=True)
