@@ -750,6 +750,46 @@ int rlvi_sample_weight_online_f64(const double *X, const double *w, double b, in
                                   double tol, int maxiter, double *losses_out, double *sample_weight,
                                   int32_t *out_iters, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The online path's whole mini-batch in ONE launch (online_sgd.hip), replaces online-learning/
+ * main.py:291-313 and :318-331 for one classifier: residuals -> sample weights -> clf.partial_fit(X, y, classes=[0, 1],
+ * sample_weight=...) -> the four counts of clf.predict(X_test) against y_test.
+ *   partial_fit is ONE pass of scikit-learn's _plain_sgd with the reference's settings (SGDClassifier(loss='log_loss',
+ *   random_state=1): L2 penalty alpha, learning rate 'optimal', an intercept, one epoch, no averaging) over the rows in
+ *   `order` (int32 [n], what scikit-learn's shuffle makes of the identity: it depends on n alone and the host computes
+ *   it; NULL: natural order).  state [d + 2] = (coef [d], intercept, t) is read (unless first != 0: the unfitted
+ *   classifier, coef 0, intercept 0, t 1) and updated in place; t grows by one per sample.
+ *   method 0: unit weights (main.py:313); 1: update_weights_rlvi (:45-58, tol, maxiter) and 2: update_weights_rrm(eps)
+ *   (:61-81, as the exact root: rlvi_rrm_update_weights_f64's rule) of the residuals -log sigmoid(X coef + intercept)
+ *   -- log 2 for every row when first != 0 (:293); 3: the weights in sample_weight.
+ *   X [n, d], y [n] in {0, 1} (as fp64; 1 is the positive class), Xt [m, d], yt [m] (m may be 0, then they may be NULL).
+ *   sample_weight [n]: receives the weights (methods 0 .. 2; may be NULL there), is read by method 3.
+ *   counts int32[4] = (tp, tn, fp, fn) of main.py:320-331 with the prediction `decision value > 0` and the NEW state.
+ *   info int32[4] = { E-step iterations (method 1) or root-find evaluations (2), 1 if RRM's rule had a root, samples
+ *   whose update was not zero, flag }; flag 1: a coefficient or the intercept is not finite (scikit-learn raises
+ *   ValueError; the state is written as it is); 2: no weights -- a residual not finite, or (1 - eps) n <= 1: no pass,
+ *   the state as it was; 3: the root-find hit its 200 evaluations (results written); 4: an index of `order` outside
+ *   [0, n) (or, stream form, a row count outside its padding): nothing is read through it, no pass.
+ *   1 <= n <= 4096, 0 <= m <= 4096, 1 <= d <= 128 (RLVI_E_LIMIT beyond); alpha > 0, 0 < eps < 1 for method 2.
+ *
+ * rlvi_online_stream_f64: T consecutive mini-batches for S <= 8 classifiers in ONE launch (main.py:288-339, the whole
+ * loop of main()), one workgroup per classifier, all reading the same data; every classifier starts unfitted.
+ *   X [T, n, d], y [T, n], Xt [T, m, d], yt [T, m] padded to the largest batch; rows int32 [T, 2] = (n_t, m_t), the
+ *   real row counts (NULL: n and m everywhere; rows beyond them are never read); orders int32 [T, n] (NULL: natural).
+ *   methods (HOST, int32 [S]) and eps (HOST, fp64 [S]; may be NULL without a method 2).
+ *   state_hist [S, T, d + 2] (the state after every batch), counts int32 [S, T, 4], weights [S, T, n] (may be NULL
+ *   without a method 3; a method 3 reads its weights there, the others write theirs), info int32 [S, T, 4].
+ *   Every (classifier, batch) has the bits of the same sequence of rlvi_online_step_f64 calls.
+ * ------------------------------------------------------------------------------------- */
+int rlvi_online_step_f64(const double *X, const double *y, const int32_t *order, int64_t n, int64_t d, int method,
+                         double eps, int first, double *state, const double *Xt, const double *yt, int64_t m,
+                         double alpha, double tol, int maxiter, double *sample_weight, int32_t *counts,
+                         int32_t *info, void *stream);
+int rlvi_online_stream_f64(const double *X, const double *y, const double *Xt, const double *yt, const int32_t *rows,
+                           const int32_t *orders, int64_t T, int64_t n, int64_t m, int64_t d, const int32_t *methods,
+                           const double *eps, int64_t S, double alpha, double tol, int maxiter, double *state_hist,
+                           int32_t *counts, double *weights, int32_t *info, void *stream);
+
 /* Measurement aid (bench.py: roofline.copy_same_bytes_us): flat copy, 16 B per lane, nontemporal loads and stores,
  * 16 waves per CU -- the plainest kernel that moves the M-step's bytes.  16-byte aligned, bytes a multiple of 16. */
 int rlvi_stream_copy(void *dst, const void *src, size_t bytes, void *stream);

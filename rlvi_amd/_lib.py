@@ -126,6 +126,11 @@ SIGNATURES = {
     "rlvi_rrm_logistic_regression_batch_f64": (_int, [_vp, _vp, _i64, _i64, _i64, _f64, _int, _f64, _f64, _vp, _vp, _vp,
                                                       _vp, _vp]),
     "rlvi_sample_weight_online_f64": (_int, [_vp, _vp, _f64, _int, _i64, _i64, _f64, _int, _vp, _vp, _vp, _vp]),
+    "rlvi_online_step_f64": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _f64, _int, _vp, _vp, _vp, _i64, _f64, _f64, _int,
+                                    _vp, _vp, _vp, _vp]),
+    "rlvi_online_stream_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_f64), _i64, _f64, _f64, _int,
+                                      _vp, _vp, _vp, _vp, _vp]),
     "rlvi_stream_copy": (_int, [_vp, _vp, ctypes.c_size_t, _vp]),
 }
 

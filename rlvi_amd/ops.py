@@ -933,6 +933,153 @@ def sample_weight_online(X, coef, intercept=0.0, first=False, tol=1e-3, maxiter=
     return out, losses, iters
 
 
+# ---- the online path's mini-batch and stream (online_sgd.hip)
+ONLINE_METHODS = {"SGD": 0, "RLVI": 1, "RRM": 2, "GIVEN": 3}
+# info[..., 3] of online_step / online_stream -> (exception class -- None: RlviError --, text); read by
+# rlvi_amd.online._raise_flags
+ONLINE_FLAGS = {
+    1: (ValueError, "Floating-point under-/overflow occurred at epoch #1. Scaling input data with StandardScaler or "
+                    "MinMaxScaler might help."),
+    2: (ValueError, "{name}: no sample weights -- a residual is not finite, or (1 - eps) n <= 1"),
+    3: (None, "{name}: RRM's root-find did not end within its 200 evaluations"),
+    4: (ValueError, "{name}: an index of the order, or a row count, is out of range"),
+}
+
+
+class _Online:
+    """The two entries of online_sgd.hip, written once: what a design, a label vector, the test rows, an order and an
+    output must be -- `lead` the leading dimensions ((), or (T,) for the stream) --, and the allocation of the outputs
+    that are not given."""
+
+    def __init__(self, entry):
+        self.entry = entry
+
+    @staticmethod
+    def _f64(t, shape, what):
+        if t is None or not (_fp64(t) and tuple(t.shape) == tuple(shape)):
+            raise ValueError(f"{what} must be a contiguous fp64 device tensor of shape {list(shape)}")
+        return t
+
+    @staticmethod
+    def _i32(t, shape, what, device, optional=True, zero=False):
+        if t is None:
+            if optional:
+                return None
+            return (torch.zeros if zero else torch.empty)(shape, dtype=torch.int32, device=device)
+        if not (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+                and t.device == device):
+            raise ValueError(f"{what} must be a contiguous int32 device tensor of shape {list(shape)}")
+        return t
+
+    def inputs(self, X, y, X_test, y_test, lead):
+        """(n, d, m) of checked inputs; the test rows may both be None (m = 0)"""
+        if (X_test is None) != (y_test is None):
+            raise ValueError("X_test and y_test come together")
+        _require_gpu(*[t for t in (X, y, X_test, y_test) if t is not None])
+        k = len(lead)
+        if not (torch.is_tensor(X) and X.dim() == k + 2 and tuple(X.shape[:k]) == tuple(lead)):
+            raise ValueError(f"X must be a contiguous fp64 device tensor of shape {[*lead, 'n', 'd']}")
+        n, d = X.shape[k:]
+        self._f64(X, (*lead, n, d), "X")
+        self._f64(y, (*lead, n), "y")
+        m = 0
+        if X_test is not None:
+            if X_test.dim() != k + 2:
+                raise ValueError(f"X_test must be a contiguous fp64 device tensor of shape {[*lead, 'm', d]}")
+            m = X_test.shape[k]
+            self._f64(X_test, (*lead, m, d), "X_test")
+            self._f64(y_test, (*lead, m), "y_test")
+        return n, d, m
+
+
+_ONLINE_STEP = _Online("rlvi_online_step_f64")
+_ONLINE_STREAM = _Online("rlvi_online_stream_f64")
+
+
+def _online_method(m):
+    if isinstance(m, str):
+        if m not in ONLINE_METHODS:
+            raise ValueError(f"method must be one of {sorted(ONLINE_METHODS)} or 0 .. 3, not {m!r}")
+        return ONLINE_METHODS[m]
+    return int(m)
+
+
+def online_step(X, y, state, method="SGD", eps=0.3, first=False, order=None, X_test=None, y_test=None, alpha=1e-4,
+                tol=1e-3, maxiter=100, sample_weight=None, counts=None, info=None):
+    """One mini-batch of online-learning/main.py:291-313, :318-331 for one classifier in ONE launch on device tensors
+    (rlvi_online_step_f64; no host synchronisation here): residuals -> sample weights (method 'SGD': ones, 'RLVI':
+    update_weights_rlvi, 'RRM': update_weights_rrm(eps), 'GIVEN': sample_weight as passed) -> one partial_fit pass of
+    scikit-learn's SGDClassifier(loss='log_loss', random_state=1, alpha=alpha) over the rows in `order` (int32 [n],
+    rlvi_amd.online.sgd_order(n); None: natural order) -> the counts (tp, tn, fp, fn) of the test rows under the new
+    state.  state [d + 2] = (coef, intercept, t) is updated in place (first: the unfitted classifier, whatever state
+    holds).  Returns (state, sample_weight [n], counts int32[4], info int32[4] = {E-step iterations or root-find
+    evaluations, 1 if RRM had a root, samples with a non-zero update, flag}); the flags are ONLINE_FLAGS."""
+    L = _lib.load()
+    n, d, m = _ONLINE_STEP.inputs(X, y, X_test, y_test, ())
+    _require_gpu(state)
+    _Online._f64(state, (d + 2,), "state")
+    method = _online_method(method)
+    dev = X.device
+    if sample_weight is None:
+        if method == 3:
+            raise ValueError("method 'GIVEN' needs sample_weight")
+        sample_weight = torch.empty(n, dtype=torch.float64, device=dev)
+    _require_gpu(sample_weight)
+    _Online._f64(sample_weight, (n,), "sample_weight")
+    order = _Online._i32(order, (n,), "order", dev)
+    counts = _Online._i32(counts, (4,), "counts", dev, optional=False)
+    info = _Online._i32(info, (4,), "info", dev, optional=False, zero=True)
+    _lib.check(L.rlvi_online_step_f64(_ptr(X), _ptr(y), _ptr(order), n, d, method, float(eps), 1 if first else 0,
+                                      _ptr(state), _ptr(X_test), _ptr(y_test), m, float(alpha), float(tol),
+                                      int(maxiter), _ptr(sample_weight), _ptr(counts), _ptr(info), _stream_ptr()),
+               "rlvi_online_step_f64")
+    return state, sample_weight, counts, info
+
+
+def online_stream(X, y, X_test, y_test, methods=("SGD", "RRM", "RLVI"), eps=0.3, rows=None, orders=None, alpha=1e-4,
+                  tol=1e-3, maxiter=100, weights=None, want_weights=True, state_hist=None, counts=None, info=None):
+    """The loop of online-learning/main.py:288-339 -- T consecutive mini-batches for S <= 8 classifiers -- in ONE launch
+    (rlvi_online_stream_f64), one workgroup per classifier, every classifier unfitted at the start.  X [T, n, d], y
+    [T, n], X_test [T, m, d], y_test [T, m] padded to the largest batch (the test rows may be None); rows int32 [T, 2] =
+    (n_t, m_t), the real row counts (None: all of them); orders int32 [T, n] (None: natural order).  eps: one value, or
+    one per classifier.  weights [S, T, n]: written by the methods that compute theirs, read by a 'GIVEN' (which needs
+    it); without it the weights are kept (want_weights) or not.  Returns (state_hist [S, T, d + 2], counts int32[S, T, 4],
+    weights or None, info int32[S, T, 4]); (classifier s, batch t) has the bits of the same sequence of online_step."""
+    L = _lib.load()
+    if not (torch.is_tensor(X) and X.dim() == 3):
+        raise ValueError("X must be a contiguous fp64 device tensor of shape ['T', 'n', 'd']")
+    T = X.shape[0]
+    n, d, m = _ONLINE_STREAM.inputs(X, y, X_test, y_test, (T,))
+    codes = [_online_method(v) for v in methods]
+    S = len(codes)
+    if not 1 <= S <= 8:
+        raise ValueError("1 to 8 methods are expected")
+    eps = [float(eps)] * S if isinstance(eps, (int, float)) else [float(e) for e in eps]
+    if len(eps) != S:
+        raise ValueError("eps: one value, or one per method")
+    dev = X.device
+    if weights is None and (want_weights or 3 in codes):
+        if 3 in codes:
+            raise ValueError("method 'GIVEN' needs weights [S, T, n]")
+        weights = torch.zeros((S, T, n), dtype=torch.float64, device=dev)
+    if weights is not None:
+        _require_gpu(weights)
+        _Online._f64(weights, (S, T, n), "weights")
+    if state_hist is None:
+        state_hist = torch.empty((S, T, d + 2), dtype=torch.float64, device=dev)
+    _require_gpu(state_hist)
+    _Online._f64(state_hist, (S, T, d + 2), "state_hist")
+    rows = _Online._i32(rows, (T, 2), "rows", dev)
+    orders = _Online._i32(orders, (T, n), "orders", dev)
+    counts = _Online._i32(counts, (S, T, 4), "counts", dev, optional=False)
+    info = _Online._i32(info, (S, T, 4), "info", dev, optional=False, zero=True)
+    _lib.check(L.rlvi_online_stream_f64(_ptr(X), _ptr(y), _ptr(X_test), _ptr(y_test), _ptr(rows), _ptr(orders), T, n,
+                                        m, d, (ctypes.c_int32 * S)(*codes), (ctypes.c_double * S)(*eps), S,
+                                        float(alpha), float(tol), int(maxiter), _ptr(state_hist), _ptr(counts),
+                                        _ptr(weights), _ptr(info), _stream_ptr()), "rlvi_online_stream_f64")
+    return state_hist, counts, weights, info
+
+
 def stream_copy(dst, src):
     """Measurement aid: flat nontemporal 16-B/lane copy of src into dst (same byte count, 16-byte multiples)."""
     nbytes = src.numel() * src.element_size()
