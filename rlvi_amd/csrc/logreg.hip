@@ -30,6 +30,7 @@
 // The fit itself (lg_fit and its passes, LgShared, the constants) lives in rlvi_logreg.h, which RRM's logistic
 // regression (robust_logreg.hip) shares.
 #include "rlvi_logreg.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -157,34 +158,23 @@ static int lg_check(int64_t n, int64_t d) {
     return (n <= SL_MAXN && d <= LG_MAXD) ? 0 : RLVI_E_LIMIT;
 }
 
-// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms
-template <bool BATCH = false>
-static int lg_launch(const double *X, const double *y, const double *w_in, int64_t n, int64_t d, int mode,
-                     int maxiter, double tol, double etol, int emaxiter, double creg, double *theta, double *w_out,
-                     double *losses, int32_t *info, void *ws, hipStream_t st, int64_t batch = 1) {
-    const int npad = (int)((n + 63) / 64) * 64;
-    const size_t lds = lg_lds_doubles(npad) * sizeof(double);
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    auto go = [&](auto kern) {
-        // (asked for per kernel: allow_dyn_lds keeps its once-per-device state by the kernel's address)
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, y, w_in, (int)n, (int)d,
-                      npad, mode, maxiter, tol, etol, emaxiter, creg, theta, w_out, losses, info, status,
-                      stamp_base(ws));
-    };
-    // samples per thread (1 / 4 / 16); the system of d + 1 unknowns solved padded to 4 / 16 / 24 / 32 rows; [X | 1]
-    // and the gradient's column in one 16-column block (d <= 14) or two
-#define RLVI_LG(E_)                                                     \
-    do {                                                                \
-        if (d <= 3) return go(logreg_rlvi_kernel<E_, 4, 1, BATCH>);     \
-        if (d <= 14) return go(logreg_rlvi_kernel<E_, 16, 1, BATCH>);   \
-        if (d <= 23) return go(logreg_rlvi_kernel<E_, 24, 2, BATCH>);   \
-        return go(logreg_rlvi_kernel<E_, 32, 2, BATCH>);                \
-    } while (0)
-    if (n <= SL_THREADS) RLVI_LG(1);
-    if (n <= 4 * SL_THREADS) RLVI_LG(4);
-    RLVI_LG(16);
-#undef RLVI_LG
+// all three entries: mode 0 with one workgroup or (BATCH) one per problem of the batch, mode 1 (w_in the weights, no
+// w_out) with one.  `required` is the entry's own list; the rest of the contract is the same.
+template <bool BATCH>
+static int lg_entry(std::initializer_list<const void *> required, const double *X, const double *y,
+                    const double *w_in, int64_t batch, int64_t n, int64_t d, int mode, int maxiter, double tol,
+                    double etol, int emaxiter, double creg, double *theta, double *w_out, double *losses, int32_t *info,
+                    void *ws, void *stream) {
+    if (const int e = sl_check_args(required, batch, n, d, maxiter >= 0 && emaxiter >= 0 && creg > 0.0,
+                                    n <= SL_MAXN && d <= LG_MAXD, {X, y, w_in, theta, w_out, losses}, {info}, ws))
+        return e;
+    const int npad = sl_pad64(n);
+    return sl_logreg_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(logreg_rlvi_kernel<F::E, F::DS, F::NB, BATCH>, batch, lg_lds_doubles(npad) * sizeof(double),
+                         static_cast<hipStream_t>(stream), X, y, w_in, (int)n, (int)d, npad, mode, maxiter, tol, etol,
+                         emaxiter, creg, theta, w_out, losses, info, sl_status(ws), stamp_base(ws));
+    });
 }
 
 }  // namespace rlvi
@@ -196,32 +186,20 @@ extern "C" int rlvi_logistic_regression_check(int64_t n, int64_t d) { return lg_
 extern "C" int rlvi_logistic_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
                                             double tol, double estep_tol, int estep_maxiter, double C, double *theta,
                                             double *weights, double *losses, int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0 || !(C > 0.0)) return RLVI_E_SHAPE;
-    if (lg_check(n, d)) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, theta, weights, losses}, info, ws)) return RLVI_E_ALIGN;
-    return lg_launch<>(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses, info,
-                     ws, static_cast<hipStream_t>(stream));
+    return lg_entry<false>({X, y, theta, weights, info, ws}, X, y, nullptr, 1, n, d, 0, maxiter, tol, estep_tol,
+                           estep_maxiter, C, theta, weights, losses, info, ws, stream);
 }
 
 extern "C" int rlvi_logistic_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
                                                   int maxiter, double tol, double estep_tol, int estep_maxiter,
                                                   double C, double *theta, double *weights, double *losses,
                                                   int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0 || !(C > 0.0)) return RLVI_E_SHAPE;
-    if (batch > SL_MAXBATCH || lg_check(n, d)) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, theta, weights, losses}, info, ws)) return RLVI_E_ALIGN;
-    return lg_launch<true>(X, y, nullptr, n, d, 0, maxiter, tol, estep_tol, estep_maxiter, C, theta, weights, losses,
-                           info, ws, static_cast<hipStream_t>(stream), batch);
+    return lg_entry<true>({X, y, theta, weights, info, ws}, X, y, nullptr, batch, n, d, 0, maxiter, tol, estep_tol,
+                          estep_maxiter, C, theta, weights, losses, info, ws, stream);
 }
 
 extern "C" int rlvi_logistic_fit_f64(const double *X, const double *y, const double *w, int64_t n, int64_t d, double C,
                                      double *theta, double *losses, int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({X, y, w, theta, losses, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || !(C > 0.0)) return RLVI_E_SHAPE;
-    if (lg_check(n, d)) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, w, theta, losses}, info, ws)) return RLVI_E_ALIGN;
-    return lg_launch<>(X, y, w, n, d, 1, 0, 0.0, 0.0, 0, C, theta, nullptr, losses, info, ws,
-                     static_cast<hipStream_t>(stream));
+    return lg_entry<false>({X, y, w, theta, losses, info, ws}, X, y, w, 1, n, d, 1, 0, 0.0, 0.0, 0, C, theta, nullptr,
+                           losses, info, ws, stream);
 }

@@ -35,6 +35,7 @@
 // PCA: an exactly repeated largest eigenvalue leaves the direction unpinned (any vector of its eigenspace is an
 // answer; the one returned is what the sweeps happen to leave).
 #include "rlvi_rrm.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -664,38 +665,30 @@ static int mo_check(int64_t n, int64_t d) {
     return (n >= 2 && n <= SL_MAXN && d <= MO_MAXD && n * d <= MO_MAXND) ? 0 : RLVI_E_LIMIT;
 }
 
-// one workgroup, or (BATCH) one per problem of the batch: ONE dispatch rule for both forms (MODE 3 .. 5: n_eff is eps)
-template <int MODE, bool BATCH = false>
-static int mo_launch(const double *X, const double *theta_init, int64_t n, int64_t d, int maxiter, double tol,
-                     double etol, int emaxiter, double n_eff, double *theta, double *w_out, int32_t *info, void *ws,
-                     hipStream_t st, int64_t batch = 1) {
-    const size_t lds = mo_lds_bytes(n * d);
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    auto go = [&](auto kern) {
-        // (asked for per kernel: allow_dyn_lds keeps its once-per-device state by the kernel's address)
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, theta_init, (int)n, (int)d,
-                      maxiter, tol, etol, emaxiter, n_eff, theta, w_out, info, status);
-    };
-    // samples per thread (1 / 4 / 16); the d x d algebra padded to 2 / 4 / 8
-#define RLVI_MO(E_)                                                     \
-    do {                                                                \
-        if (d <= 2) return go(moments_rlvi_kernel<MODE, E_, 2, BATCH>); \
-        if (d <= 4) return go(moments_rlvi_kernel<MODE, E_, 4, BATCH>); \
-        return go(moments_rlvi_kernel<MODE, E_, 8, BATCH>);             \
-    } while (0)
-    if (n <= SL_THREADS) RLVI_MO(1);
-    if (n <= 4 * SL_THREADS) RLVI_MO(4);
-    RLVI_MO(16);
-#undef RLVI_MO
+// every entry of the six modes: one workgroup, or (BATCH) one per problem of the batch (MODE 3 .. 5: n_eff is eps; no
+// estep_tol / estep_maxiter -- the rule is a root, not a fixed point).  theta_init is optional, and checked when given.
+template <int MODE, bool BATCH>
+static int mo_entry(const double *X, const double *theta_init, int64_t batch, int64_t n, int64_t d,
+                    int maxiter, double tol, double etol, int emaxiter, double n_eff, double *theta, double *weights,
+                    int32_t *info, void *ws, void *stream) {
+    if (const int e = sl_check_args({X, theta, weights, info, ws}, batch, n, d, maxiter >= 0 && emaxiter >= 0,
+                                    mo_check(n, d) == 0, {X, theta_init, theta, weights}, {info}, ws))
+        return e;
+    return sl_moments_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(moments_rlvi_kernel<MODE, F::E, F::DS, BATCH>, batch, mo_lds_bytes(n * d),
+                         static_cast<hipStream_t>(stream), X, theta_init, (int)n, (int)d, maxiter, tol, etol, emaxiter,
+                         n_eff, theta, weights, info, sl_status(ws));
+    });
 }
 
-static int mo_args(const double *sample, int64_t n, int64_t d, int maxiter, int estep_maxiter, const double *theta_init,
-                   double *theta, double *weights, int32_t *info, void *ws, int64_t batch = 1) {
-    if (sl_any_null({sample, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
-    if (batch > SL_MAXBATCH || mo_check(n, d)) return RLVI_E_LIMIT;
-    return sl_misaligned({sample, theta_init, theta, weights}, info, ws) ? RLVI_E_ALIGN : 0;
+// the two weight rules on their own (the slots alone in LDS: no request for more)
+template <class GO>
+static int mo_weights_entry(const double *losses, int64_t n, bool params_ok, double *out, int32_t *info, void *ws,
+                            GO &&go) {
+    if (const int e = sl_check_args({losses, out, info, ws}, 1, n, 1, params_ok, n <= SL_MAXN, {losses, out}, {info}, ws))
+        return e;
+    return sl_samples_per_thread(n, go);
 }
 
 }  // namespace rlvi
@@ -705,132 +698,95 @@ using namespace rlvi;
 extern "C" int rlvi_moments_check(int64_t n, int64_t d) { return mo_check(n, d); }
 
 extern "C" int rlvi_robust_mean_f64(const double *sample, int64_t n, int64_t d, int maxiter, double tol,
-                                    double estep_tol, int estep_maxiter, double *theta, double *weights,
-                                    int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws)) return e;
-    return mo_launch<0>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights, info, ws,
-                        static_cast<hipStream_t>(stream));
+                                    double estep_tol, int estep_maxiter, double *theta, double *weights, int32_t *info,
+                                    void *ws, void *stream) {
+    return mo_entry<0, false>(sample, nullptr, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights,
+                              info, ws, stream);
 }
 
 extern "C" int rlvi_robust_pca_f64(const double *sample, int64_t n, int64_t d, int maxiter, double tol,
                                    const double *theta_init, double estep_tol, int estep_maxiter, double *theta,
                                    double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, theta_init, theta, weights, info, ws)) return e;
-    return mo_launch<1>(sample, theta_init, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights, info,
-                        ws, static_cast<hipStream_t>(stream));
+    return mo_entry<1, false>(sample, theta_init, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights,
+                              info, ws, stream);
 }
 
 extern "C" int rlvi_robust_covariance_f64(const double *sample, int64_t n, int64_t d, double n_eff, int maxiter,
                                           double tol, double estep_tol, int estep_maxiter, double *theta,
                                           double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws)) return e;
-    return mo_launch<2>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta, weights, info, ws,
-                        static_cast<hipStream_t>(stream));
+    return mo_entry<2, false>(sample, nullptr, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta, weights,
+                              info, ws, stream);
 }
 
 extern "C" int rlvi_robust_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter,
                                           double tol, double estep_tol, int estep_maxiter, double *theta,
                                           double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws, batch)) return e;
-    return mo_launch<0, true>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights, info,
-                              ws, static_cast<hipStream_t>(stream), batch);
+    return mo_entry<0, true>(sample, nullptr, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights,
+                             info, ws, stream);
 }
 
 extern "C" int rlvi_robust_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, int maxiter,
                                          double tol, const double *theta_init, double estep_tol, int estep_maxiter,
                                          double *theta, double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, theta_init, theta, weights, info, ws, batch))
-        return e;
-    return mo_launch<1, true>(sample, theta_init, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta, weights,
-                              info, ws, static_cast<hipStream_t>(stream), batch);
+    return mo_entry<1, true>(sample, theta_init, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, 0.0, theta,
+                             weights, info, ws, stream);
 }
 
 extern "C" int rlvi_robust_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double n_eff,
                                                 int maxiter, double tol, double estep_tol, int estep_maxiter,
-                                                double *theta, double *weights, int32_t *info, void *ws,
-                                                void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, estep_maxiter, nullptr, theta, weights, info, ws, batch)) return e;
-    return mo_launch<2, true>(sample, nullptr, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta, weights,
-                              info, ws, static_cast<hipStream_t>(stream), batch);
+                                                double *theta, double *weights, int32_t *info, void *ws, void *stream) {
+    return mo_entry<2, true>(sample, nullptr, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, n_eff, theta,
+                             weights, info, ws, stream);
 }
 
 extern "C" int rlvi_update_weights_constrained_f64(const double *losses, int64_t n, double n_eff, double tol,
                                                    int maxiter, double *out, int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({losses, out, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || maxiter < 0) return RLVI_E_SHAPE;
-    if (n > SL_MAXN) return RLVI_E_LIMIT;
-    if (sl_misaligned({losses, out}, info, ws)) return RLVI_E_ALIGN;
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = mo_lds_bytes(0);
-    auto go = [&](auto kern) {
-        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, losses, (int)n, n_eff, tol, maxiter, out, info, status);
-    };
-    if (n <= SL_THREADS) return go(moments_uwc_kernel<1>);
-    if (n <= 4 * SL_THREADS) return go(moments_uwc_kernel<4>);
-    return go(moments_uwc_kernel<16>);
+    return mo_weights_entry(losses, n, maxiter >= 0, out, info, ws, [&](auto f) {
+        return sl_launch_plain(moments_uwc_kernel<decltype(f)::E>, 1, mo_lds_bytes(0), static_cast<hipStream_t>(stream),
+                               losses, (int)n, n_eff, tol, maxiter, out, info, sl_status(ws));
+    });
 }
 
-// ---- Robust Risk Minimization: estep_tol / estep_maxiter have no counterpart (the rule is a root, not a fixed point)
+// ---- Robust Risk Minimization
 extern "C" int rlvi_rrm_mean_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
                                  double *theta, double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws)) return e;
-    return mo_launch<3>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                        static_cast<hipStream_t>(stream));
+    return mo_entry<3, false>(sample, nullptr, 1, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_pca_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
                                 const double *theta_init, double *theta, double *weights, int32_t *info, void *ws,
                                 void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, theta_init, theta, weights, info, ws)) return e;
-    return mo_launch<4>(sample, theta_init, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                        static_cast<hipStream_t>(stream));
+    return mo_entry<4, false>(sample, theta_init, 1, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_covariance_f64(const double *sample, int64_t n, int64_t d, double eps, int maxiter, double tol,
                                        double *theta, double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws)) return e;
-    return mo_launch<5>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                        static_cast<hipStream_t>(stream));
+    return mo_entry<5, false>(sample, nullptr, 1, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_mean_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
-                                       int maxiter, double tol, double *theta, double *weights, int32_t *info,
-                                       void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws, batch)) return e;
-    return mo_launch<3, true>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                              static_cast<hipStream_t>(stream), batch);
+                                       int maxiter, double tol, double *theta, double *weights, int32_t *info, void *ws,
+                                       void *stream) {
+    return mo_entry<3, true>(sample, nullptr, batch, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_pca_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
-                                      int maxiter, double tol, const double *theta_init, double *theta,
-                                      double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, theta_init, theta, weights, info, ws, batch)) return e;
-    return mo_launch<4, true>(sample, theta_init, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                              static_cast<hipStream_t>(stream), batch);
+                                      int maxiter, double tol, const double *theta_init, double *theta, double *weights,
+                                      int32_t *info, void *ws, void *stream) {
+    return mo_entry<4, true>(sample, theta_init, batch, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
+                             stream);
 }
 
 extern "C" int rlvi_rrm_covariance_batch_f64(const double *sample, int64_t batch, int64_t n, int64_t d, double eps,
                                              int maxiter, double tol, double *theta, double *weights, int32_t *info,
                                              void *ws, void *stream) {
-    if (const int e = mo_args(sample, n, d, maxiter, 0, nullptr, theta, weights, info, ws, batch)) return e;
-    return mo_launch<5, true>(sample, nullptr, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws,
-                              static_cast<hipStream_t>(stream), batch);
+    return mo_entry<5, true>(sample, nullptr, batch, n, d, maxiter, tol, 0.0, 0, eps, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_update_weights_f64(const double *losses, int64_t n, double eps, double *out, int32_t *info,
                                            void *ws, void *stream) {
-    if (sl_any_null({losses, out, info, ws})) return RLVI_E_NULL;
-    if (n <= 0) return RLVI_E_SHAPE;
-    if (n > SL_MAXN) return RLVI_E_LIMIT;
-    if (sl_misaligned({losses, out}, info, ws)) return RLVI_E_ALIGN;
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = mo_lds_bytes(0);
-    auto go = [&](auto kern) {
-        return launch(kern, dim3(1), dim3(SL_THREADS), lds, st, losses, (int)n, eps, out, info, status);
-    };
-    if (n <= SL_THREADS) return go(moments_rrm_weights_kernel<1>);
-    if (n <= 4 * SL_THREADS) return go(moments_rrm_weights_kernel<4>);
-    return go(moments_rrm_weights_kernel<16>);
+    return mo_weights_entry(losses, n, true, out, info, ws, [&](auto f) {
+        return sl_launch_plain(moments_rrm_weights_kernel<decltype(f)::E>, 1, mo_lds_bytes(0),
+                               static_cast<hipStream_t>(stream), losses, (int)n, eps, out, info, sl_status(ws));
+    });
 }

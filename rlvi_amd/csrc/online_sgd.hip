@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "rlvi_rrm.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -333,23 +334,12 @@ static double on_optimal_init(double alpha) {
     return 1.0 / (eta0 * alpha);
 }
 
-static int on_launch(OnArgs &a, int S, hipStream_t st) {
-    a.npad = (a.n + 63) / 64 * 64;
+static int on_launch(OnArgs &a, int S, void *stream) {
+    a.npad = sl_pad64(a.n);
     a.oinit = on_optimal_init(a.alpha);
-    const size_t lds = on_lds_bytes(a.npad);
-    auto go = [&](auto kern) {
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3((unsigned)S), dim3(SL_THREADS), lds, st, a);
-    };
-    if (a.n <= SL_THREADS) return go(online_sgd_kernel<1>);
-    if (a.n <= 4 * SL_THREADS) return go(online_sgd_kernel<4>);
-    return go(online_sgd_kernel<16>);
-}
-
-static bool on_misaligned32(std::initializer_list<const void *> ptrs) {
-    for (const void *p : ptrs)
-        if ((uintptr_t)p & 3) return true;
-    return false;
+    return sl_samples_per_thread(a.n, [&](auto f) {
+        return sl_launch(online_sgd_kernel<decltype(f)::E>, S, on_lds_bytes(a.npad), static_cast<hipStream_t>(stream), a);
+    });
 }
 
 }  // namespace rlvi
@@ -360,13 +350,13 @@ extern "C" int rlvi_online_step_f64(const double *X, const double *y, const int3
                                     int method, double eps, int first, double *state, const double *Xt,
                                     const double *yt, int64_t m, double alpha, double tol, int maxiter,
                                     double *sample_weight, int32_t *counts, int32_t *info, void *stream) {
-    if (sl_any_null({X, y, state, counts, info}) || (m > 0 && sl_any_null({Xt, yt})) || (method == 3 && !sample_weight))
-        return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || m < 0 || maxiter < 0 || method < 0 || method > 3 || !(alpha > 0.0) ||
-        (method == 2 && !(eps > 0.0 && eps < 1.0)))
-        return RLVI_E_SHAPE;
-    if (n > SL_MAXN || m > SL_MAXN || d > ON_MAXD) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, state, Xt, yt, sample_weight}) || on_misaligned32({order, counts, info})) return RLVI_E_ALIGN;
+    const bool params_ok = m >= 0 && maxiter >= 0 && method >= 0 && method <= 3 && alpha > 0.0 &&
+                           (method != 2 || (eps > 0.0 && eps < 1.0));
+    if (const int e = sl_check_args({X, y, state, counts, info, sl_when(m > 0, Xt), sl_when(m > 0, yt),
+                                     sl_when(method == 3, sample_weight)},
+                                    1, n, d, params_ok, n <= SL_MAXN && m <= SL_MAXN && d <= ON_MAXD,
+                                    {X, y, state, Xt, yt, sample_weight}, {order, counts, info}))
+        return e;
     OnArgs a = {};
     a.X = X; a.y = y; a.Xt = Xt; a.yt = yt;
     a.rows = nullptr; a.orders = order;
@@ -375,7 +365,7 @@ extern "C" int rlvi_online_step_f64(const double *X, const double *y, const int3
     a.T = 1; a.n = (int)n; a.m = (int)m; a.d = (int)d; a.first = first ? 1 : 0; a.maxiter = maxiter;
     a.alpha = alpha; a.tol = tol;
     a.method[0] = method; a.eps[0] = eps;
-    return on_launch(a, 1, static_cast<hipStream_t>(stream));
+    return on_launch(a, 1, stream);
 }
 
 extern "C" int rlvi_online_stream_f64(const double *X, const double *y, const double *Xt, const double *yt,
@@ -383,9 +373,11 @@ extern "C" int rlvi_online_stream_f64(const double *X, const double *y, const do
                                       int64_t d, const int32_t *methods, const double *eps, int64_t S, double alpha,
                                       double tol, int maxiter, double *state_hist, int32_t *counts, double *weights,
                                       int32_t *info, void *stream) {
-    if (sl_any_null({X, y, methods, state_hist, counts, info}) || (m > 0 && sl_any_null({Xt, yt}))) return RLVI_E_NULL;
-    if (T <= 0 || S <= 0 || n <= 0 || d <= 0 || m < 0 || maxiter < 0 || !(alpha > 0.0)) return RLVI_E_SHAPE;
-    if (S > ON_MAXS || T > ON_MAXT || n > SL_MAXN || m > SL_MAXN || d > ON_MAXD) return RLVI_E_LIMIT;
+    if (const int e = sl_check_values({X, y, methods, state_hist, counts, info, sl_when(m > 0, Xt), sl_when(m > 0, yt)},
+                                      1, n, d, T > 0 && S > 0 && m >= 0 && maxiter >= 0 && alpha > 0.0,
+                                      S <= ON_MAXS && T <= ON_MAXT && n <= SL_MAXN && m <= SL_MAXN && d <= ON_MAXD))
+        return e;
+    // the classifiers' own checks: behind the limits (S), in front of the alignment
     OnArgs a = {};
     for (int64_t s = 0; s < S; ++s) {
         const int me = methods[s];
@@ -395,13 +387,12 @@ extern "C" int rlvi_online_stream_f64(const double *X, const double *y, const do
         a.method[s] = me;
         a.eps[s] = eps ? eps[s] : 0.0;
     }
-    if (sl_misaligned({X, y, Xt, yt, state_hist, weights}) || on_misaligned32({rows, orders, counts, info}))
-        return RLVI_E_ALIGN;
+    if (sl_misaligned({X, y, Xt, yt, state_hist, weights}, {rows, orders, counts, info})) return RLVI_E_ALIGN;
     a.X = X; a.y = y; a.Xt = Xt; a.yt = yt;
     a.rows = rows; a.orders = orders;
     a.state_in = nullptr; a.state_out = state_hist;
     a.weights = weights; a.counts = counts; a.info = info;
     a.T = (int)T; a.n = (int)n; a.m = (int)m; a.d = (int)d; a.first = 1; a.maxiter = maxiter;
     a.alpha = alpha; a.tol = tol;
-    return on_launch(a, (int)S, static_cast<hipStream_t>(stream));
+    return on_launch(a, (int)S, stream);
 }

@@ -1,6 +1,7 @@
 // The weighted least-squares fit of the one-workgroup linear regressions, ONE copy: what linreg_rlvi_kernel
 // (standard.hip) and the RRM / Huber regressions (robust_linreg.hip) share.
-//   * SlShared and its LDS size (sl_lds_doubles), the trip sizes SL_XS / SL_RU / SL_GU, the lab stamps (SL_STAMP);
+//   * SlShared (its LDS size is sl_lds_doubles of rlvi_sl_launch.h), the trip sizes SL_XS / SL_RU / SL_GU, the lab
+//     stamps (SL_STAMP);
 //   * sl_wls: the weighted Gram matrix [X | y]^T W [X | y] on the fp64 matrix cores + the one-wave L D L^T solve with
 //     the scale-free pivot test; sl_residuals: the squared residuals and the weighted variance;
 //   * sl_ldlt_factor / sl_ldlt_substitute: the one-wave solve split in two, for a system that is factored once and
@@ -40,11 +41,6 @@ struct SlShared {
     int *flag;          // [4]
     double *x1s;        // [1024][8]  columns 16 .. 23 of [X | y] (resident design with two column blocks)
 };
-
-// linreg_rlvi_kernel's LDS in doubles: wsh, rsh, the solve's block, x1s where the resident design has a second block
-__host__ __device__ constexpr size_t sl_lds_doubles(int npad, bool x1s) {
-    return 2 * (size_t)npad + SL_SOLVE_DOUBLES + (x1s ? 1024 * 8 : 0);
-}
 
 // theta = argmin sum_i w_i (y_i - x_i.theta)^2 from the weights in sh.wsh -> sh.th[0 .. d).  Returns false (on
 // every thread) when a pivot is not safely positive.  All threads call.  DS: the system is solved padded to DS >= d

@@ -6,18 +6,17 @@
 //     Gram partials into it (sl_gram_collect), the pivot floor and the L D L^T solve on one wave (sl_ldlt_solve);
 //   * the E-step's fixed point on the threads' own samples (sl_estep_fixed_point) and the outer stop test
 //     (sl_theta_moved);
-//   * the argument checks of the extern "C" entries (sl_any_null, sl_misaligned) and the batch forms' limit
-//     (SL_MAXBATCH: the estimator kernels as `template <..., bool BATCH>`, workgroup b on problem b of a contiguous
-//     batch behind pointer offsets at kernel entry; a slice of a batch is 8-byte aligned, which is what every fp64
-//     load of these kernels -- all of them scalar doubles -- and sl_misaligned ask).
+//   * the batch forms' limit (SL_MAXBATCH: the estimator kernels as `template <..., bool BATCH>`, workgroup b on
+//     problem b of a contiguous batch behind pointer offsets at kernel entry; a slice of a batch is 8-byte aligned,
+//     which is what every fp64 load of these kernels -- all of them scalar doubles -- asks).
+// Device code and the constants it shares with the host.  The host side of the entries -- the argument checks, the
+// launch, the dispatch tables -- is rlvi_sl_launch.h.
 // linreg_rlvi_kernel (standard.hip) is held to the instructions it had: it takes the offsets, the pivot floor and
 // sl_block_sum2 from here and keeps the Gram collection, the solve, the fixed point and the stop test in place --
 // each of them called from here moves its register allocation, and single cells of its sweep by up to 2 % either way
 // (profiles/r17_sl_header.md).  Its fit (sl_wls, sl_residuals: that text, verbatim) lives in rlvi_linreg.h, which the
 // RRM and Huber regressions (robust_linreg.hip) share; RRM's weight rule is rlvi_rrm.h.
 #pragma once
-#include <initializer_list>
-
 #include "rlvi_common.h"
 
 namespace rlvi {
@@ -305,20 +304,6 @@ __device__ __forceinline__ bool sl_theta_moved(const double *th, int D, double t
     const double tn = lane < D ? th[lane] : 0.0, tp = lane < D ? th[SL_DP + lane] : 0.0;
     const double dn = wave_sum((tn - tp) * (tn - tp)), pn = wave_sum(tp * tp);
     return !(sqrt(dn) / sqrt(pn) <= tol);
-}
-
-// ---- the extern "C" entries' argument checks (a null pointer counts as aligned: an optional argument passes)
-inline bool sl_any_null(std::initializer_list<const void *> ptrs) {
-    for (const void *p : ptrs)
-        if (!p) return true;
-    return false;
-}
-// the fp64 arrays on 8 bytes, info on 4, the workspace on 256
-inline bool sl_misaligned(std::initializer_list<const void *> f64, const void *info = nullptr,
-                          const void *ws = nullptr) {
-    for (const void *p : f64)
-        if ((uintptr_t)p & 7) return true;
-    return ((uintptr_t)info & 3) || ((uintptr_t)ws & 255);
 }
 
 }  // namespace rlvi

@@ -21,6 +21,7 @@
 
 #include "rlvi_linreg.h"
 #include "rlvi_rrm.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -449,73 +450,45 @@ __global__ __launch_bounds__(SL_THREADS) void linreg_huber_kernel(
     }
 }
 
-// the dispatch table of sl_linreg_launch (standard.hip): samples per thread, the padded system, the column blocks,
-// the resident design
-#define RL_DISPATCH(KERN, BATCH_)                                                          \
-    do {                                                                                   \
-        if (res) {                                                                         \
-            if (d <= 12) return go(KERN<4, 12, 1, true, BATCH_>);                          \
-            if (d <= 15) return go(KERN<4, 16, 1, true, BATCH_>);                          \
-            if (d <= 20) return go(KERN<4, 20, 2, true, BATCH_>);                          \
-            return go(KERN<4, 24, 2, true, BATCH_>);                                       \
-        }                                                                                  \
-        if (n <= 4 * SL_THREADS) return go(KERN<4, 32, 2, false, BATCH_>);                 \
-        if (d <= 12) return go(KERN<16, 12, 1, false, BATCH_>);                            \
-        if (d <= 15) return go(KERN<16, 16, 1, false, BATCH_>);                            \
-        if (d <= 20) return go(KERN<16, 20, 2, false, BATCH_>);                            \
-        if (d <= 24) return go(KERN<16, 24, 2, false, BATCH_>);                            \
-        return go(KERN<16, 32, 2, false, BATCH_>);                                         \
-    } while (0)
-
-struct RlShape {
-    bool res;
-    int npad;
-    size_t lds;
-};
-static RlShape rl_shape(int64_t n, int64_t d) {
-    const bool two = d >= 16, res = n <= 4 * SL_THREADS && d <= 23;
-    const int npad = res ? 1024 : (int)((n + 63) / 64) * 64;
-    return {res, npad, (sl_lds_doubles(npad, res && two) + RL_EXTRA_DOUBLES) * sizeof(double)};
-}
-
-template <bool BATCH>
-static int rl_rrm_launch(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
-                         double tol, double *theta, double *weights, int32_t *info, void *ws, hipStream_t st) {
-    const RlShape s = rl_shape(n, d);
-    const bool res = s.res;
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    auto go = [&](auto kern) {
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), s.lds, st, X, y, (int)n, (int)d, s.npad,
-                      maxiter, tol, eps, theta, weights, info, status);
-    };
-    RL_DISPATCH(linreg_rrm_kernel, BATCH);
-}
-
-template <bool BATCH>
-static int rl_huber_launch(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double c,
-                           double sigma0, int maxiter, double *theta, double *scale, int32_t *info, void *ws,
-                           hipStream_t st) {
-    const RlShape s = rl_shape(n, d);
-    const bool res = s.res;
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    const double alpha = rlvi_huber_alpha(c);
-    auto go = [&](auto kern) {
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), s.lds, st, X, y, (int)n, (int)d, s.npad,
-                      maxiter, c, sigma0, alpha, theta, scale, info, status);
-    };
-    RL_DISPATCH(linreg_huber_kernel, BATCH);
-}
-#undef RL_DISPATCH
-
+// Both forms of both estimators: one workgroup, or (BATCH) one per problem of the batch.  The contract is
+// rlvi_linear_regression_f64's with the estimator's own parameters (params_ok) and its second output (out2: RRM's
+// weights, Huber's scale); the table and the shape are standard.hip's (sl_linreg_form, sl_linreg_shape), with the rule's
+// slots or Huber's 1 / D behind SlShared's LDS.
 static int rl_args(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, int maxiter, bool params_ok,
                    double *theta, double *out2, int32_t *info, void *ws) {
-    if (sl_any_null({X, y, theta, out2, info, ws})) return RLVI_E_NULL;
-    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || !params_ok) return RLVI_E_SHAPE;
-    if (batch > SL_MAXBATCH || n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
-    return sl_misaligned({X, y, theta, out2}, info, ws) ? RLVI_E_ALIGN : 0;
+    return sl_check_args({X, y, theta, out2, info, ws}, batch, n, d, maxiter >= 0 && params_ok,
+                         n <= SL_MAXN && d < SL_DP, {X, y, theta, out2}, {info}, ws);
 }
+
+template <bool BATCH>
+static int rl_rrm_entry(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double eps,
+                        int maxiter, double tol, double *theta, double *weights, int32_t *info, void *ws,
+                        void *stream) {
+    if (const int e = rl_args(X, y, batch, n, d, maxiter, rl_eps_ok(eps, n), theta, weights, info, ws)) return e;
+    const SlLinregShape s = sl_linreg_shape(n, d, RL_EXTRA_DOUBLES);
+    return sl_linreg_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(linreg_rrm_kernel<F::E, F::DS, F::NB, F::RES, BATCH>, batch, s.lds,
+                         static_cast<hipStream_t>(stream), X, y, (int)n, (int)d, s.npad, maxiter, tol, eps, theta, weights,
+                         info, sl_status(ws));
+    });
+}
+
+template <bool BATCH>
+static int rl_huber_entry(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double c,
+                          double sigma0, int maxiter, double *theta, double *scale, int32_t *info, void *ws,
+                          void *stream) {
+    if (const int e = rl_args(X, y, batch, n, d, maxiter, c > 0.0 && sigma0 > 0.0, theta, scale, info, ws)) return e;
+    const SlLinregShape s = sl_linreg_shape(n, d, RL_EXTRA_DOUBLES);
+    const double alpha = rlvi_huber_alpha(c);
+    return sl_linreg_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(linreg_huber_kernel<F::E, F::DS, F::NB, F::RES, BATCH>, batch, s.lds,
+                         static_cast<hipStream_t>(stream), X, y, (int)n, (int)d, s.npad, maxiter, c, sigma0, alpha, theta,
+                         scale, info, sl_status(ws));
+    });
+}
+
 }  // namespace rlvi
 
 using namespace rlvi;
@@ -531,31 +504,23 @@ extern "C" double rlvi_huber_alpha(double c) {
 extern "C" int rlvi_rrm_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double eps,
                                               int maxiter, double tol, double *theta, double *weights, int32_t *info,
                                               void *ws, void *stream) {
-    if (const int e = rl_args(X, y, 1, n, d, maxiter, rl_eps_ok(eps, n), theta, weights, info, ws)) return e;
-    return rl_rrm_launch<false>(X, y, 1, n, d, eps, maxiter, tol, theta, weights, info, ws,
-                                static_cast<hipStream_t>(stream));
+    return rl_rrm_entry<false>(X, y, 1, n, d, eps, maxiter, tol, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n,
                                                     int64_t d, double eps, int maxiter, double tol, double *theta,
                                                     double *weights, int32_t *info, void *ws, void *stream) {
-    if (const int e = rl_args(X, y, batch, n, d, maxiter, rl_eps_ok(eps, n), theta, weights, info, ws)) return e;
-    return rl_rrm_launch<true>(X, y, batch, n, d, eps, maxiter, tol, theta, weights, info, ws,
-                               static_cast<hipStream_t>(stream));
+    return rl_rrm_entry<true>(X, y, batch, n, d, eps, maxiter, tol, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_huber_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double c,
                                                 double sigma0, int maxiter, double *theta, double *scale, int32_t *info,
                                                 void *ws, void *stream) {
-    if (const int e = rl_args(X, y, 1, n, d, maxiter, c > 0.0 && sigma0 > 0.0, theta, scale, info, ws)) return e;
-    return rl_huber_launch<false>(X, y, 1, n, d, c, sigma0, maxiter, theta, scale, info, ws,
-                                  static_cast<hipStream_t>(stream));
+    return rl_huber_entry<false>(X, y, 1, n, d, c, sigma0, maxiter, theta, scale, info, ws, stream);
 }
 
 extern "C" int rlvi_huber_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n,
                                                       int64_t d, double c, double sigma0, int maxiter, double *theta,
                                                       double *scale, int32_t *info, void *ws, void *stream) {
-    if (const int e = rl_args(X, y, batch, n, d, maxiter, c > 0.0 && sigma0 > 0.0, theta, scale, info, ws)) return e;
-    return rl_huber_launch<true>(X, y, batch, n, d, c, sigma0, maxiter, theta, scale, info, ws,
-                                 static_cast<hipStream_t>(stream));
+    return rl_huber_entry<true>(X, y, batch, n, d, c, sigma0, maxiter, theta, scale, info, ws, stream);
 }

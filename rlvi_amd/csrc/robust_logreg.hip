@@ -7,12 +7,13 @@
 // on 100 .. 200 x 2 designs, up to 101 fits per call.  Both halves are on the device already, one copy of each:
 // the weighted fit is lg_fit (rlvi_logreg.h: damped Newton on the matrix cores, to the minimiser liblinear
 // approximates), the weight rule is mo_estep_rrm (rlvi_rrm.h: the exact entropy root).  This kernel keeps the two in
-// one persistent workgroup of four waves with the LDS block and the dispatch table of logreg_rlvi_kernel (logreg.hip)
-// and the rule's slot area, with a parity of its own, behind it.  Every decision is taken by every thread from the
-// same LDS totals; sums are fp64 in a fixed order: same inputs, same bits.  Everything read from LDS is written by
-// this workgroup first.
+// one persistent workgroup of four waves with the LDS block of logreg_rlvi_kernel (logreg.hip), its dispatch table
+// (sl_logreg_form, rlvi_sl_launch.h) and the rule's slot area, with a parity of its own, behind it.  Every decision is
+// taken by every thread from the same LDS totals; sums are fp64 in a fixed order: same inputs, same bits.  Everything
+// read from LDS is written by this workgroup first.
 #include "rlvi_logreg.h"
 #include "rlvi_rrm.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -130,38 +131,23 @@ __global__ __launch_bounds__(SL_THREADS) void logreg_rrm_kernel(
     }
 }
 
-// one workgroup, or (BATCH) one per problem of the batch: the dispatch table of lg_launch (logreg.hip)
+// both entries: one workgroup, or (BATCH) one per problem of the batch.  The contract of
+// rlvi_logistic_regression_f64 and the eps rule of the RRM regressions; sl_logreg_form is logreg.hip's table.
 template <bool BATCH>
-static int rg_launch(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
-                     double tol, double creg, double *theta, double *weights, int32_t *info, void *ws, hipStream_t st) {
-    const int npad = (int)((n + 63) / 64) * 64;
-    const size_t lds = rg_lds_doubles(npad) * sizeof(double);
-    int32_t *status = &static_cast<WsHeader *>(ws)->status;
-    auto go = [&](auto kern) {
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d, npad,
-                      maxiter, tol, eps, creg, theta, weights, info, status);
-    };
-#define RLVI_RG(E_)                                                    \
-    do {                                                               \
-        if (d <= 3) return go(logreg_rrm_kernel<E_, 4, 1, BATCH>);     \
-        if (d <= 14) return go(logreg_rrm_kernel<E_, 16, 1, BATCH>);   \
-        if (d <= 23) return go(logreg_rrm_kernel<E_, 24, 2, BATCH>);   \
-        return go(logreg_rrm_kernel<E_, 32, 2, BATCH>);                \
-    } while (0)
-    if (n <= SL_THREADS) RLVI_RG(1);
-    if (n <= 4 * SL_THREADS) RLVI_RG(4);
-    RLVI_RG(16);
-#undef RLVI_RG
-}
-
-// the checks of rlvi_logistic_regression_f64 and the eps rule of the RRM regressions
-static int rg_args(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double eps, int maxiter,
-                   double C, double *theta, double *weights, int32_t *info, void *ws) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || !(C > 0.0) || !rl_eps_ok(eps, n)) return RLVI_E_SHAPE;
-    if (batch > SL_MAXBATCH || n > SL_MAXN || d > LG_MAXD) return RLVI_E_LIMIT;
-    return sl_misaligned({X, y, theta, weights}, info, ws) ? RLVI_E_ALIGN : 0;
+static int rg_entry(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, double eps,
+                    int maxiter, double tol, double creg, double *theta, double *weights, int32_t *info, void *ws,
+                    void *stream) {
+    if (const int e = sl_check_args({X, y, theta, weights, info, ws}, batch, n, d,
+                                    maxiter >= 0 && creg > 0.0 && rl_eps_ok(eps, n), n <= SL_MAXN && d <= LG_MAXD,
+                                    {X, y, theta, weights}, {info}, ws))
+        return e;
+    const int npad = sl_pad64(n);
+    return sl_logreg_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(logreg_rrm_kernel<F::E, F::DS, F::NB, BATCH>, batch, rg_lds_doubles(npad) * sizeof(double),
+                         static_cast<hipStream_t>(stream), X, y, (int)n, (int)d, npad, maxiter, tol, eps, creg, theta,
+                         weights, info, sl_status(ws));
+    });
 }
 
 }  // namespace rlvi
@@ -171,16 +157,12 @@ using namespace rlvi;
 extern "C" int rlvi_rrm_logistic_regression_f64(const double *X, const double *y, int64_t n, int64_t d, double eps,
                                                 int maxiter, double tol, double C, double *theta, double *weights,
                                                 int32_t *info, void *ws, void *stream) {
-    if (const int e = rg_args(X, y, 1, n, d, eps, maxiter, C, theta, weights, info, ws)) return e;
-    return rg_launch<false>(X, y, 1, n, d, eps, maxiter, tol, C, theta, weights, info, ws,
-                            static_cast<hipStream_t>(stream));
+    return rg_entry<false>(X, y, 1, n, d, eps, maxiter, tol, C, theta, weights, info, ws, stream);
 }
 
 extern "C" int rlvi_rrm_logistic_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n,
                                                       int64_t d, double eps, int maxiter, double tol, double C,
                                                       double *theta, double *weights, int32_t *info, void *ws,
                                                       void *stream) {
-    if (const int e = rg_args(X, y, batch, n, d, eps, maxiter, C, theta, weights, info, ws)) return e;
-    return rg_launch<true>(X, y, batch, n, d, eps, maxiter, tol, C, theta, weights, info, ws,
-                           static_cast<hipStream_t>(stream));
+    return rg_entry<true>(X, y, batch, n, d, eps, maxiter, tol, C, theta, weights, info, ws, stream);
 }

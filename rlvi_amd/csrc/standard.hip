@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "rlvi_linreg.h"
+#include "rlvi_sl_launch.h"
 
 namespace rlvi {
 
@@ -318,76 +319,47 @@ extern "C" int rlvi_linear_regression_check(int64_t n, int64_t d) {
     return (n <= SL_MAXN && d < SL_DP) ? 0 : RLVI_E_LIMIT;
 }
 
-// the launch of a checked call: one workgroup, or (BATCH) one per problem -- ONE dispatch rule for both forms
+// both forms of the entry: one workgroup, or (BATCH) one per problem -- the single form is the batch form with batch = 1
 template <bool BATCH>
-static int sl_linreg_launch(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, int maxiter,
-                            double tol, double estep_tol, int estep_maxiter, double *theta, double *weights,
-                            int32_t *info, void *ws, hipStream_t st) {
-    // (samples per thread: four up to n = 1024, sixteen beyond; the system solved padded to 12 / 16 / 20 / 24 / 32 rows;
-    //  one or two 16-column blocks of [X | y]; the design resident on the chip -- registers + LDS -- when n <= 1024
-    //  and d <= 23)
-    const bool two = d >= 16;                                     // column d (= y) needs the second block
-    const bool res = n <= 4 * SL_THREADS && d <= 23;
-    const int npad_x = res ? 1024 : (int)((n + 63) / 64) * 64;
-    const size_t lds = sl_lds_doubles(npad_x, res && two) * sizeof(double);
-    auto go = [&](auto kern) {
-        if (const int e = allow_dyn_lds(kern, 150 * 1024)) return e;
-        return launch(kern, dim3(BATCH ? (unsigned)batch : 1u), dim3(SL_THREADS), lds, st, X, y, (int)n, (int)d,
-                      npad_x, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info,
-                      reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + WS_SCRATCH_OFF));
-    };
-    if (res) {
-        if (d <= 12) return go(linreg_rlvi_kernel<4, 12, 1, true, BATCH>);
-        if (d <= 15) return go(linreg_rlvi_kernel<4, 16, 1, true, BATCH>);
-        if (d <= 20) return go(linreg_rlvi_kernel<4, 20, 2, true, BATCH>);
-        return go(linreg_rlvi_kernel<4, 24, 2, true, BATCH>);
-    }
-    if (n <= 4 * SL_THREADS) return go(linreg_rlvi_kernel<4, 32, 2, false, BATCH>);      // d = 24 .. 31
-    if (d <= 12) return go(linreg_rlvi_kernel<16, 12, 1, false, BATCH>);
-    if (d <= 15) return go(linreg_rlvi_kernel<16, 16, 1, false, BATCH>);
-    if (d <= 20) return go(linreg_rlvi_kernel<16, 20, 2, false, BATCH>);
-    if (d <= 24) return go(linreg_rlvi_kernel<16, 24, 2, false, BATCH>);
-    return go(linreg_rlvi_kernel<16, 32, 2, false, BATCH>);
+static int sl_linreg_entry(const double *X, const double *y, int64_t batch, int64_t n, int64_t d, int maxiter,
+                           double tol, double estep_tol, int estep_maxiter, double *theta, double *weights,
+                           int32_t *info, void *ws, void *stream) {
+    if (const int e = sl_check_args({X, y, theta, weights, info, ws}, batch, n, d, maxiter >= 0 && estep_maxiter >= 0,
+                                    n <= SL_MAXN && d < SL_DP, {X, y, theta, weights}, {info}, ws))
+        return e;
+    const SlLinregShape s = sl_linreg_shape(n, d, 0);
+    return sl_linreg_form(n, d, [&](auto f) {
+        using F = decltype(f);
+        return sl_launch(linreg_rlvi_kernel<F::E, F::DS, F::NB, F::RES, BATCH>, batch, s.lds,
+                         static_cast<hipStream_t>(stream), X, y, (int)n, (int)d, s.npad, maxiter, tol, estep_tol,
+                         estep_maxiter, theta, weights, info, stamp_base(ws));
+    });
 }
 
 extern "C" int rlvi_linear_regression_f64(const double *X, const double *y, int64_t n, int64_t d, int maxiter,
                                           double tol, double estep_tol, int estep_maxiter, double *theta,
                                           double *weights, int32_t *info, void *ws, void *stream) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
-    if (n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
-    return sl_linreg_launch<false>(X, y, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
-                                   static_cast<hipStream_t>(stream));
+    return sl_linreg_entry<false>(X, y, 1, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
+                                  stream);
 }
 
 extern "C" int rlvi_linear_regression_batch_f64(const double *X, const double *y, int64_t batch, int64_t n, int64_t d,
                                                 int maxiter, double tol, double estep_tol, int estep_maxiter,
                                                 double *theta, double *weights, int32_t *info, void *ws,
                                                 void *stream) {
-    if (sl_any_null({X, y, theta, weights, info, ws})) return RLVI_E_NULL;
-    if (batch <= 0 || n <= 0 || d <= 0 || maxiter < 0 || estep_maxiter < 0) return RLVI_E_SHAPE;
-    if (batch > SL_MAXBATCH || n > SL_MAXN || d >= SL_DP) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, y, theta, weights}, info, ws)) return RLVI_E_ALIGN;
-    return sl_linreg_launch<true>(X, y, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
-                                  static_cast<hipStream_t>(stream));
+    return sl_linreg_entry<true>(X, y, batch, n, d, maxiter, tol, estep_tol, estep_maxiter, theta, weights, info, ws,
+                                 stream);
 }
 
 extern "C" int rlvi_sample_weight_online_f64(const double *X, const double *w, double b, int first, int64_t n,
                                              int64_t d, double tol, int maxiter, double *losses_out,
                                              double *sample_weight, int32_t *out_iters, void *stream) {
-    if (!sample_weight || (!first && sl_any_null({X, w}))) return RLVI_E_NULL;
-    if (n <= 0 || d <= 0 || maxiter < 0) return RLVI_E_SHAPE;
-    if (n > SL_MAXN) return RLVI_E_LIMIT;
-    if (sl_misaligned({X, w, sample_weight, losses_out})) return RLVI_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define RLVI_OW(E_)                                                                                         \
-    return launch(online_weight_kernel<E_>, dim3(1), dim3(SL_THREADS), 0, st, X, w, b, first, (int)n, (int)d, \
-                  tol, maxiter, losses_out, sample_weight, out_iters)
-    if (n <= SL_THREADS) RLVI_OW(1);
-    if (n <= 2 * SL_THREADS) RLVI_OW(2);
-    if (n <= 4 * SL_THREADS) RLVI_OW(4);
-    if (n <= 8 * SL_THREADS) RLVI_OW(8);
-    RLVI_OW(16);
-#undef RLVI_OW
+    if (const int e = sl_check_args({sample_weight, sl_when(!first, X), sl_when(!first, w)}, 1, n, d, maxiter >= 0,
+                                    n <= SL_MAXN, {X, w, sample_weight, losses_out}))
+        return e;
+    // (static LDS: no request for more)
+    return sl_per_thread<1, 2, 4, 8, 16>(n, [&](auto f) {
+        return sl_launch_plain(online_weight_kernel<decltype(f)::E>, 1, 0, static_cast<hipStream_t>(stream), X, w, b,
+                               first, (int)n, (int)d, tol, maxiter, losses_out, sample_weight, out_iters);
+    });
 }
